@@ -18,7 +18,11 @@ visible; under torchrun WORLD_SIZE must equal --gpus. A barrier + synchronize
 brackets the timed steps and the max time over ranks is reported; byte and
 record totals are summed over ranks.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md for every field). A plain run
+sets up, warms up, times --steps steps and prints the headline; --full adds
+every other leg and check (verification, CPU baseline, host path, shape legs,
+whole-batch decode legs, probes, scatter). --dump-outputs DIR writes a fixed
+sample of what the last timed step computed as DIR/<name>.npy (encdec mode).
 """
 from __future__ import annotations
 
@@ -57,6 +61,16 @@ def parse_args(argv=None):
                    help="rehearsal of the N > 1 code paths on a one-GPU box: every rank on GPU 0, "
                         "gloo instead of RCCL (the scatter staged through host memory); the "
                         "numbers are not a measurement")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure too: the verification of every record, "
+                        "the CPU baseline, the host-path leg, the shape legs (--legs), the whole-batch "
+                        "decode legs, the chunk zero-copy decode, the HBM probes and (N > 1) the scatter "
+                        "leg. Without it a run sets up, warms up, times --steps steps and prints the line; "
+                        "the fields of what did not run are null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step left in its output "
+                        "buffers as DIR/<name>.npy (float32 bytes, float64 offsets): a fixed seeded "
+                        "sample of records of the chunks the output slots still hold (Bench.dump_outputs)")
     p.add_argument("--steps", type=int, default=3)
     p.add_argument("--warmup", type=int, default=1)
     p.add_argument("--records", type=int, default=1 << 20, help="records per GPU")
@@ -153,9 +167,10 @@ def parse_args(argv=None):
                    help="with two metadata streams, a chunk's single-launch decode waits for the "
                         "previous chunk's (and its guarded launch): the guard never queues for "
                         "LDS behind the other slot's persistent decode")
-    p.add_argument("--decode-leg", choices=["both", "zero_copy", "materialising"], default="both",
+    p.add_argument("--decode-leg", choices=["both", "zero_copy", "materialising"], default=None,
                    help="decode mode: run one leg only (PMC passes attribute a kernel's traffic "
-                        "to one leg)")
+                        "to one leg); default: both with --full, else the line's own leg "
+                        "(materialising)")
     p.add_argument("--zc-forms", choices=["all", "default"], default="all",
                    help="decode legs: the zero-copy leg times the default list forms and, for "
                         "comparison, the table forms and speculation off (all), or the default forms "
@@ -175,6 +190,53 @@ def P(t):
     return t.data_ptr()
 
 
+# --dump-outputs: the sample is the same for every run and build (its own
+# seed, not --seed: the inputs follow --seed, the places looked at do not)
+DUMP_SEED = 0x686F6E75
+DUMP_RECORDS = 4096  # sampled records, split between the chunks still held
+DUMP_BYTES = 512     # sampled bytes of each sampled record's encoding and of its payload
+DUMP_TABLE = 4096    # leading entries of an ACL / region table
+
+
+def dump_prefix():
+    """File-name prefix of this rank's --dump-outputs files (none at N = 1)."""
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    return f"rank{os.environ.get('RANK', '0')}_" if world > 1 else ""
+
+
+def dump_sample(n, k):
+    """(sorted indices of min(n, k) of n records, DUMP_BYTES // 2 fractions in
+    [0, 1) of a record's length), from DUMP_SEED."""
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(n, min(n, k), replace=False)).astype(np.int64)
+    return idx, rng.random(DUMP_BYTES // 2)
+
+
+def sample_bytes(arena, start, length, frac):
+    """float32 [k, DUMP_BYTES]: of each byte range [start, start + length) of
+    the device arena its first and last DUMP_BYTES / 4 bytes and the bytes at
+    the fractions frac of its length between them (ranges shorter than that
+    repeat their bytes; an empty one gives -1). Positions are clamped to the
+    arena, so a record whose status is not OK reads garbage, never out of it."""
+    dev = arena.device
+    q = DUMP_BYTES // 4
+    ln = length.clamp(min=1)[:, None]
+    j = torch.arange(q, dtype=torch.int64, device=dev)[None, :]
+    f = torch.from_numpy(frac).to(dev)[None, :]
+    mid = torch.minimum((f * ln.double()).long(), ln - 1)
+    rel = torch.cat([j % ln, mid, (length[:, None] - q + j).clamp(min=0) % ln], dim=1)
+    pos = (start[:, None] + rel).clamp(min=0, max=arena.numel() - 1)
+    v = arena[pos].float()
+    v[length <= 0] = -1.0
+    return v
+
+
+def save_dump(path, name, t, dtype):
+    """DIR/<name>.npy from a device or host tensor, as float32 or float64."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.cpu().numpy().astype(dtype)))
+
+
 class Slot:
     """Output buffers + codec context of one in-flight chunk."""
 
@@ -189,6 +251,7 @@ class Slot:
         self.dacl, self.dreg, self.data = E(20 * acl_cap), E(4 * reg_cap), E(data_cap + pad[1])[pad[1]:]
         self.totals = E(32)
         self.free = None  # event: the slot's last copy finished
+        self.holds = None  # (a, b, step): the chunk last issued into the slot
 
 
 class Bench:
@@ -320,6 +383,7 @@ class Bench:
         self.events = None
         self.last = None
         self.nchunk = 0  # chunks issued so far, across steps: slots alternate globally
+        self.step_no = 0  # steps issued so far (Slot.holds)
         self.enc_done = None  # the last issued chunk's encode copy (--meta-beside decode)
         self.dec_done = None  # the last issued chunk's single-launch decode (--decode-chain)
         # --copy-order ahead: the last chunk's decode copy, issued after the
@@ -352,6 +416,7 @@ class Bench:
         is the AND of its answers."""
         ok = True
         pending = None
+        self.step_no += 1
         for a, b in self.chunks:
             sl = self._issue(a, b, timed)
             if check is not None:
@@ -395,6 +460,7 @@ class Bench:
         sl = self.slots[k]
         sm, sc = self.sms[k % len(self.sms)], self.sc
         self.nchunk += 1
+        sl.holds = (a, b, self.step_no)
         c = sl.codec.ctx
         if sl.free is not None:
             sm.wait_event(sl.free)
@@ -550,6 +616,51 @@ class Bench:
             _lib.check(self.lib.honu_ctx_get_param(sl.codec.ctx, b"recoveries", ctypes.byref(v)), "param")
             total += v.value
         return total
+
+    def dump_outputs(self, path, prefix=""):
+        """--dump-outputs: what the last step left for its caller, as
+        DIR/<prefix>chunk<first record>_<name>.npy. The output slots are
+        reused, so of a step's chunks only the last ones (one per slot) are
+        still there; of each, a sample of records fixed by DUMP_SEED:
+          records   float64 [k]       their indices in the batch
+          out_off   float64 [k, 2]    start and end of the encoded record in the chunk's arena
+          status    float32 [k]       encode status
+          encoded   float32 [k, 512]  bytes of the encoded record (sample_bytes)
+        and
+          rows      float32 [k, 352]  the decoded Metadata() row's bytes
+          info      float32 [k, 32]   the record info's bytes (Data() offset, length, statuses)
+          data      float32 [k, 512]  bytes of the materialised Data() (sample_bytes)
+          totals    float64 [3]       ACL table entries, region table entries, data arena bytes
+          acl_table     float32 [4096, 20]  the bytes of the ACL table's leading entries
+          region_table  float32 [4096, 4]   those of the region table's; -1 past the last entry."""
+        torch.cuda.synchronize()
+        held = sorted(((sl.holds[0], sl.holds[1], sl) for sl in self.slots
+                       if sl.holds is not None and sl.holds[2] == self.step_no),
+                      key=lambda x: x[0])
+        for a, b, sl in held:
+            n = b - a
+            idx, frac = dump_sample(n, DUMP_RECORDS // len(held))
+            name = f"{prefix}chunk{a}_"
+            i = torch.from_numpy(idx).to(self.dev)
+            off = sl.out_off[: 8 * (n + 1)].view(torch.int64)
+            start, end = off[i], off[i + 1]
+            save_dump(path, name + "records", i + a, np.float64)
+            save_dump(path, name + "out_off", torch.stack([start, end], dim=1), np.float64)
+            save_dump(path, name + "status", sl.status[: 4 * n].view(torch.int32)[i], np.float32)
+            save_dump(path, name + "encoded", sample_bytes(sl.out, start, end - start, frac), np.float32)
+            info = sl.dinfo[: 32 * n].view(torch.int64).view(n, 4)[i]
+            save_dump(path, name + "rows", sl.dmeta[: 352 * n].view(n, 352)[i], np.float32)
+            save_dump(path, name + "info", sl.dinfo[: 32 * n].view(n, 32)[i], np.float32)
+            save_dump(path, name + "data", sample_bytes(sl.data, info[:, 0], info[:, 1], frac), np.float32)
+            tot = sl.totals[:24].view(torch.int64)
+            save_dump(path, name + "totals", tot, np.float64)
+            for what, t, width, count in (("acl_table", sl.dacl, 20, int(tot[0])),
+                                          ("region_table", sl.dreg, 4, int(tot[1]))):
+                # a fixed shape whatever the count (the default list forms write no entry)
+                rows = torch.full((DUMP_TABLE, width), -1.0, dtype=torch.float32)
+                m = min(count, DUMP_TABLE, t.numel() // width)
+                rows[:m] = t[: width * m].view(m, width).float().cpu()
+                save_dump(path, name + what, rows, np.float32)
 
     def fused_decode(self, n):
         # beside the decode copy the persistent single-launch grid costs the copy more
@@ -1043,7 +1154,7 @@ class DecodeBench:
                 f"of one resident records arena, {leg}")
 
     def run(self, steps, warmup):
-        leg = getattr(self.args, "decode_leg", "both")
+        leg = getattr(self.args, "decode_leg", None) or "both"
         zc = mat = None
         zc_ok = mat_ok = True
         if leg in ("both", "zero_copy"):
@@ -1300,6 +1411,16 @@ def dry_run(args, world, rank):
         print(json.dumps({"dry_run": True, "ranks": world, "shards": shards}), flush=True)
 
 
+def headline_only(args):
+    """A run without --full: set-up, warm-up, the timed steps, --dump-outputs,
+    the line. Everything measured or checked beside them is switched off here
+    (the rest of what --full adds, in encdec_mode, looks at args.full itself)."""
+    args.no_cpu_baseline = args.no_verify = args.no_host_path = args.no_decode_legs = True
+    args.legs = "none"
+    if args.decode_leg is None:
+        args.decode_leg = "materialising"
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
@@ -1315,6 +1436,12 @@ def main(argv=None):
     if args.dry_run:
         dry_run(args, world, rank)
         return
+    if args.dump_outputs and args.mode != "encdec":
+        print("bench.py: --dump-outputs writes the encode + decode step's outputs (--mode encdec only)",
+              file=sys.stderr)
+        sys.exit(2)
+    if not args.full:
+        headline_only(args)
     if args.shared_gpu:  # rehearsal: every rank on GPU 0 (gloo below)
         local = 0
     if local >= torch.cuda.device_count():
@@ -1490,6 +1617,7 @@ def decode_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
         "warmup": args.warmup,
         "ms_per_step": ms,
         "higher_is_better": True,
+        "full": bool(args.full),
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "u8",
@@ -1668,6 +1796,7 @@ def encode_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
         "warmup": args.warmup,
         "ms_per_step": leg["ms_per_step"],
         "higher_is_better": True,
+        "full": bool(args.full),
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "u8",
@@ -1742,11 +1871,13 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
     enc_bytes = [2 * bench.chunk_payload[i % len(bench.chunks)] for i in range(len(enc_ms))]
     enc_gbs = sum(enc_bytes) / (sum(enc_ms) / 1e3) / 1e9
     dec_gbs = sum(enc_bytes) / (sum(dec_ms) / 1e3) / 1e9
+    if args.dump_outputs:  # before anything below reuses the output slots
+        bench.dump_outputs(args.dump_outputs, dump_prefix())
     verified = None if args.no_verify else bench.verify()
-    zc = bench.zero_copy_decode()
     ok_all = all_ok(verified)
-    probe = hbm_probe(bench.codec, bench.dev)
-    # the legs after the timed steps: none of them changes the numbers above
+    # --full only, from here to the decode legs: none of it changes the numbers above
+    zc = bench.zero_copy_decode() if args.full else None
+    probe = hbm_probe(bench.codec, bench.dev) if args.full else None
     bench.payload = None  # the scatter leg keeps the output slots, nothing else
     gc.collect()
     torch.cuda.empty_cache()
@@ -1754,9 +1885,9 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
     # moves (the 4 GiB probe's best form is faster than any
     # copy of a chunk's 2 x 12 GB; profiles/r06/copy_attr/)
     probe_chunk = hbm_probe(bench.codec, bench.dev, nbytes=max(bench.chunk_payload) // 16 * 16, reps=3,
-                            modes=(2, 4), blocks=(1, 2))
+                            modes=(2, 4), blocks=(1, 2)) if args.full else None
     scatter = None
-    if dist is not None:
+    if dist is not None and args.full:
         arena = off = None
         if rank == 0:  # the chunk zero_copy_decode left encoded in slot 0
             a, b, sl = bench.zc_chunk
@@ -1779,7 +1910,7 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
         host_path = host_path_leg(_Estimate(args, rank, world), args, local, world, gather_max, all_ok)
     if rank != 0:
         return None
-    if decode is not None and decode.get("materialising") is not None:  # the copy's achievable rate too
+    if probe and decode is not None and decode.get("materialising") is not None:  # the copy's achievable rate too
         mr = decode["materialising"]["roofline"]
         mr["achievable"] = probe["copy_gbs"]
         mr["frac_of_achievable"] = mr["achieved"] / probe["copy_gbs"]
@@ -1804,6 +1935,7 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
         "warmup": args.warmup,
         "ms_per_step": step_s * 1e3,
         "higher_is_better": True,
+        "full": bool(args.full),
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "u8",
@@ -1843,10 +1975,10 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
             "peak": HBM_PEAK_GBS,
             "unit": "GB/s",
             "frac": dom_gbs / HBM_PEAK_GBS,
-            "achievable": probe["copy_gbs"],
-            "frac_of_achievable": dom_gbs / probe["copy_gbs"],
-            "achievable_at_launch_bytes": probe_chunk["copy_gbs"],
-            "frac_of_achievable_at_launch_bytes": dom_gbs / probe_chunk["copy_gbs"],
+            "achievable": probe and probe["copy_gbs"],
+            "frac_of_achievable": probe and dom_gbs / probe["copy_gbs"],
+            "achievable_at_launch_bytes": probe_chunk and probe_chunk["copy_gbs"],
+            "frac_of_achievable_at_launch_bytes": probe_chunk and dom_gbs / probe_chunk["copy_gbs"],
             "traffic": traffic,
             "traffic_source": "profiles/pmc_traffic.json" if traffic else None,
             "traffic_commit": pmc_commit(workload),
@@ -1862,11 +1994,11 @@ def encdec_mode(args, rank, local, world, dist, barrier, gather_max, all_ok):
             "step_hbm_gbs_algorithmic": 4 * bench.total_rec_bytes / step_s / 1e9,
             "hbm_probe": probe,
             "hbm_probe_at_launch_bytes": probe_chunk,
-            "zero_copy_decode_records_per_s": zc["records_per_s"],
-            "zero_copy_decode_ms_per_chunk": zc["ms"],
-            "zero_copy_decode_chunk_records": zc["records"],
-            "zero_copy_decode_cold_records_per_s": zc["cold_records_per_s"],
-            "zero_copy_decode_cold_ms_per_chunk": zc["cold_ms"],
+            "zero_copy_decode_records_per_s": zc and zc["records_per_s"],
+            "zero_copy_decode_ms_per_chunk": zc and zc["ms"],
+            "zero_copy_decode_chunk_records": zc and zc["records"],
+            "zero_copy_decode_cold_records_per_s": zc and zc["cold_records_per_s"],
+            "zero_copy_decode_cold_ms_per_chunk": zc and zc["cold_ms"],
         },
         "verified": ok_all,
         "verified_scope": None if ok_all is None else Bench.VERIFIED_SCOPE,

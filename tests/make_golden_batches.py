@@ -13,6 +13,7 @@ give for it, as raw little-endian files plus a SHA-256 manifest:
   <name>.rows_table.bin / .acl_table.bin / .regions_table.bin   the same rows
     and tables with every list in its table (context params acl_inplace 0,
     regions_inplace 0)
+  (an output longer than PART bytes: <name>.<suffix>.part<k>.bin, see PART)
   totals (manifest): ACL entries, regions, data bytes of the default forms,
     then the table forms' ACL entries and regions
 Encode fixtures regenerate their input from the seeded generator (or
@@ -110,6 +111,43 @@ def outputs(name):
 
 NAMES = list(ENCODE) + ["malformed"]
 
+# No committed file is larger than 1 MiB: an output longer than PART bytes is
+# stored as <name>.<suffix>.part<k>.bin, k = 0, 1, ..., of PART bytes each (the
+# last one shorter); the manifest's SHA-256 is that of the whole output.
+PART = 1 << 19
+
+
+def _paths(name, suf):
+    """(the one-file path, the part paths that exist) of an output."""
+    parts = []
+    while os.path.exists(os.path.join(OUT, f"{name}.{suf}.part{len(parts)}.bin")):
+        parts.append(os.path.join(OUT, f"{name}.{suf}.part{len(parts)}.bin"))
+    return os.path.join(OUT, f"{name}.{suf}.bin"), parts
+
+
+def read_file(name, suf):
+    """The bytes of a committed output, whichever way it is stored."""
+    whole, parts = _paths(name, suf)
+    data = b""
+    for path in parts or [whole]:
+        with open(path, "rb") as fh:
+            data += fh.read()
+    return data
+
+
+def write_file(name, suf, data):
+    whole, parts = _paths(name, suf)
+    for path in parts + [whole]:
+        if os.path.exists(path):
+            os.remove(path)
+    if len(data) <= PART:
+        with open(whole, "wb") as fh:
+            fh.write(data)
+        return
+    for k in range(0, len(data), PART):
+        with open(os.path.join(OUT, f"{name}.{suf}.part{k // PART}.bin"), "wb") as fh:
+            fh.write(data[k:k + PART])
+
 
 def main():
     os.makedirs(OUT, exist_ok=True)
@@ -119,8 +157,7 @@ def main():
         entry = {"params": ENCODE.get(name, {"malformed_records": "tests/make_golden_batches.py"}),
                  "totals": tot, "sha256": {}}
         for suf, data in files.items():
-            with open(os.path.join(OUT, f"{name}.{suf}.bin"), "wb") as fh:
-                fh.write(data)
+            write_file(name, suf, data)
             entry["sha256"][suf] = hashlib.sha256(data).hexdigest()
         manifest[name] = entry
     with open(os.path.join(OUT, "manifest.json"), "w") as fh:

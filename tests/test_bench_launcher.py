@@ -87,7 +87,7 @@ def test_two_ranks_rehearsal_on_one_gpu():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    r = _run(["--gpus", "2", "--shared-gpu", "--shape", "small", "--records", "8192", "--steps", "2",
+    r = _run(["--gpus", "2", "--shared-gpu", "--full", "--shape", "small", "--records", "8192", "--steps", "2",
               "--warmup", "1", "--no-cpu-baseline", "--legs", "small,mixed_encode"], timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -16,8 +16,7 @@ MANIFEST = json.load(open(os.path.join(BATCHES, "manifest.json")))
 
 
 def _file(name, suf):
-    with open(os.path.join(BATCHES, f"{name}.{suf}.bin"), "rb") as fh:
-        return fh.read()
+    return mk.read_file(name, suf)  # (an output over 1 MiB is stored in parts)
 
 
 @pytest.mark.parametrize("name", mk.NAMES)

@@ -7,7 +7,7 @@ out=$1; a=$2; b=$3; rounds=$4; shift 4
 mkdir -p "$out"
 for r in $(seq 1 "$rounds"); do
   for lib in "$a" "$b"; do
-    HONU_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python bench.py "$@" --no-cpu-baseline \
+    HONU_LIB_PATH=$(realpath "$lib") timeout -k 10 300 python bench.py --full "$@" --no-cpu-baseline \
         --no-host-path --no-decode-legs > "$out/run.json" 2> "$out/run.err"
     python -c "
 import json, sys

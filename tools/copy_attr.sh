@@ -19,7 +19,7 @@ G4="TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_WRREQ_LEVEL_sum TCC_CYCLE_sum"
 G5="TCC_EA0_WRREQ_STALL_sum TCC_BUSY_sum TCC_CYCLE_sum TA_BUSY_sum TA_DATA_STALLED_BY_TC_CYCLES_sum GRBM_GUI_ACTIVE"
 timeout -k 10 200 python3 tools/copy_alone.py > $out/alone_plain.json 2> $out/alone_plain.err || exit 1
 tools/pmc_passes.sh $out/alone "$G1" "$G2" "$G3" "$G4" "$G5" -- python3 tools/copy_alone.py > $out/alone.log 2>&1 || exit 2
-tools/pmc_passes.sh $out/pipe "$G1" "$G2" "$G3" "$G4" "$G5" -- python3 bench.py --no-cpu-baseline --no-host-path \
+tools/pmc_passes.sh $out/pipe "$G1" "$G2" "$G3" "$G4" "$G5" -- python3 bench.py --full --no-cpu-baseline --no-host-path \
   --no-decode-legs --legs none > $out/pipe.log 2>&1 || exit 3
 python3 tools/copy_attr.py $out/alone $out/pipe > $out/summary.json || exit 4
 exit 0

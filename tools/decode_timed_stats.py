@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timed launches of `bench.py --mode decode` cut out of its rocprofv3 kernel
+"""Timed launches of `bench.py --full --mode decode` cut out of its rocprofv3 kernel
 trace, so the committed stats reproduce the line's rooflines:
 
   zero copy      k_decode_fused launches over the whole batch: the first is the

@@ -9,7 +9,7 @@ set -u
 out=gpurun_out/final
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout -k 10 400 python bench.py > $out/bench.json 2> $out/bench.err || exit 1
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/prof -o r01 --output-format csv -- python3 bench.py > $out/prof_bench.log 2>&1 || exit 1
-tools/pmc_passes.sh $out/pmc "FETCH_SIZE" "WRITE_SIZE" -- python3 bench.py --no-cpu-baseline > $out/pmc.log 2>&1 || exit 1
+timeout -k 10 400 python bench.py --full > $out/bench.json 2> $out/bench.err || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/prof -o r01 --output-format csv -- python3 bench.py --full > $out/prof_bench.log 2>&1 || exit 1
+tools/pmc_passes.sh $out/pmc "FETCH_SIZE" "WRITE_SIZE" -- python3 bench.py --full --no-cpu-baseline > $out/pmc.log 2>&1 || exit 1
 tools/shape_sweep.sh $out/shapes || exit 1

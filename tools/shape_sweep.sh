@@ -9,7 +9,7 @@ out=$1; shift
 mkdir -p "$out"
 for spec in small:1048576 medium:1048576 large:1048576 xlarge:65536 mixed:1048576; do
   shape=${spec%%:*}; n=${spec##*:}
-  timeout -k 10 300 python bench.py --shape "$shape" --records "$n" --cpu-seconds 8 "$@" \
+  timeout -k 10 300 python bench.py --full --shape "$shape" --records "$n" --cpu-seconds 8 "$@" \
     > "$out/$shape.json" 2> "$out/$shape.err"
   rc=$?
   echo "$shape rc=$rc"

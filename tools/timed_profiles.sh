@@ -13,7 +13,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for shape in $shapes; do
   timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $out/prof_$shape -o run --output-format csv \
-    -- python3 bench.py --shape $shape --no-cpu-baseline > $out/bench_prof_$shape.json 2> $out/prof_$shape.log || exit 1
+    -- python3 bench.py --full --shape $shape --no-cpu-baseline > $out/bench_prof_$shape.json 2> $out/prof_$shape.log || exit 1
   tr=$(find $out/prof_$shape -name '*kernel_trace.csv' | head -n 1)
   st=$(find $out/prof_$shape -name '*kernel_stats.csv' | head -n 1)
   cp "$st" $out/kernel_stats_$shape.csv
