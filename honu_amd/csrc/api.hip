@@ -389,6 +389,7 @@ int32_t honu_encode_sizes(honu_ctx *ctx, const honu_meta *d_meta, uint64_t var_l
                           uint64_t *d_sizes, int32_t *d_status, void *stream) {
     if (!ctx) return arg_fail("ctx");
     if (n && (!d_meta || !d_payload_off || !d_sizes)) return arg_fail("null pointer");
+    if (!aligned(d_meta, 16)) return arg_fail("rows must be 16-byte aligned");
     if (!aligned(d_acl, 4) || !aligned(d_regions, 4)) return arg_fail("tables must be 4-byte aligned");
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_encode_sizes_grp(d_meta, var_len, d_acl, acl_len, d_regions, regions_len,
@@ -415,6 +416,8 @@ static int32_t encode_records(honu_ctx *ctx, const honu_meta *d_meta, const uint
     if (!ctx) return arg_fail("ctx");
     if (n && (!d_meta || !d_payload_off || !d_out || !d_out_off || !d_status))
         return arg_fail("null pointer");
+    if (!aligned(d_out, 16) || !aligned(d_meta, 16))
+        return arg_fail("records arena and rows must be 16-byte aligned");
     if (!aligned(d_acl, 4) || !aligned(d_regions, 4)) return arg_fail("tables must be 4-byte aligned");
     HIPCHK(hipSetDevice(ctx->device));
     if (n > ctx->max_n) return HONU_E_WORKSPACE;
@@ -483,6 +486,7 @@ static int32_t encode_payloads(honu_ctx *ctx, const uint8_t *d_payload, const ui
                                const int32_t *d_status, bool units, void *stream) {
     if (!ctx) return arg_fail("ctx");
     if (n && (!d_payload_off || !d_out || !d_out_off || !d_status)) return arg_fail("null pointer");
+    if (!aligned(d_out, 16)) return arg_fail("records arena must be 16-byte aligned");
     // the units pair completes only what its own records call left out: a
     // payload call of the other form than the context's last records call
     // would leave bytes unwritten (or write them twice) with every status OK
@@ -537,6 +541,13 @@ int32_t honu_marshal_batch(honu_ctx *ctx, const honu_meta *d_meta, const uint8_t
                            const uint8_t *d_payload, const uint64_t *d_payload_off, uint64_t n,
                            uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_off,
                            int32_t *d_status, void *stream) {
+    // the checks of the phases below, before the first of them launches: a
+    // refused call has stored nothing
+    if (!ctx) return arg_fail("ctx");
+    if (n > ctx->max_n) return HONU_E_WORKSPACE;
+    if (n && (!d_meta || !d_payload_off || !d_out || !d_out_off || !d_status)) return arg_fail("null pointer");
+    if (!aligned(d_out, 16) || !aligned(d_meta, 16))
+        return arg_fail("records arena and rows must be 16-byte aligned");
     int32_t st = honu_encode_sizes(ctx, d_meta, var_len, d_acl, acl_len, d_regions, regions_len,
                                    d_payload_off, n, d_out_off, d_status, stream);
     if (st) return st;
@@ -662,8 +673,15 @@ int32_t honu_decode_batch(honu_ctx *ctx, const uint8_t *d_rec, const uint64_t *d
     // kernels' extra waves hide the walk's latency better), always with
     // record_variant 6
     const int rv = ctx ? ctx->geom.record_variant : 0;
+    // every argument check of the phases below, before the first of them
+    // launches: a refused call has stored nothing
+    if (ctx && n > ctx->max_n) return HONU_E_WORKSPACE;
+    if (!aligned(d_rec, 16) || !aligned(d_meta, 16) || !aligned(d_info, 8))
+        return arg_fail("records arena and rows must be 16-byte aligned");
+    if (!aligned(d_acl, 4) || !aligned(d_regions, 4) || !aligned(d_data, 16))
+        return arg_fail("tables 4-byte / data arena 16-byte aligned");
+    if ((acl_cap && !d_acl) || (regions_cap && !d_regions)) return arg_fail("table");
     if (rv == 6 || (rv == 0 && n >= FUSED_DECODE_MIN_RECORDS)) {
-        if (d_data && !aligned(d_data, 16)) return arg_fail("data arena must be 16-byte aligned");
         int32_t st = honu_decode_records(ctx, d_rec, d_rec_off, n, d_meta, d_info, d_acl, acl_cap,
                                          d_regions, regions_cap, d_data != nullptr, data_cap,
                                          d_totals, stream);

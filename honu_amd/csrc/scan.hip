@@ -72,7 +72,23 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_scan_lb(const uint64_t *in, uint
         for (int c = 0; c < K; c++) x[c] = block_incl_scan(s[c], sh, &agg[c]) - s[c];
         if (threadIdx.x < HONU_WAVE) {  // wave 0: the tile's prefix across tiles
             uint64_t excl[K];
-            lb_scan<K>(S.status, t, ep, agg, excl);
+            if constexpr (K == 1) {
+                // A look-back word carries 43 value bits (lookback.h), and the
+                // one-column scan is a public entry point (honu_exclusive_scan)
+                // whose prefixes are not bounded by an arena's size: the tile's
+                // sum goes through the look-back as three limbs of 22, 21 and 21
+                // bits (three status words per tile, which scan_status_words
+                // reserves). A limb's prefix stays below 2^43 for up to 2^21
+                // tiles (2^33 rows), so the result is exact in uint64 arithmetic
+                // (modulo 2^64) whatever the values.
+                const uint64_t limb[3] = {agg[0] & ((1ull << 22) - 1), (agg[0] >> 22) & ((1ull << 21) - 1),
+                                          agg[0] >> 43};
+                uint64_t lex[3];
+                lb_scan<3>(S.status, t, ep, limb, lex);
+                excl[0] = lex[0] + (lex[1] << 22) + (lex[2] << 43);
+            } else {  // the decode's count columns: table entries and data-arena bytes, far below 2^43
+                lb_scan<K>(S.status, t, ep, agg, excl);
+            }
 #pragma unroll
             for (int c = 0; c < K; c++) {
                 if (threadIdx.x == 0) pre[c] = excl[c];
@@ -95,7 +111,8 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_scan_lb(const uint64_t *in, uint
     if (threadIdx.x < HONU_WAVE) lb_finish(S.lb, S.status, S.words, t, ntiles, gridDim.x);
 }
 
-uint64_t scan_status_words(uint64_t n) {  // the most K * tiles of any form
+uint64_t scan_status_words(uint64_t n) {  // the most words per tile * tiles of any form (three per
+                                          // tile in the one-column scan too: its limbs; t3 >= t1)
     const uint64_t t3 = (n + HONU_BLOCK * SCAN_ITEMS_3_SHORT - 1) / (HONU_BLOCK * SCAN_ITEMS_3_SHORT);
     const uint64_t t1 = (n + HONU_BLOCK * SCAN_ITEMS_1 - 1) / (HONU_BLOCK * SCAN_ITEMS_1);
     return 3 * t3 > t1 ? 3 * t3 + 3 : t1 + 3;

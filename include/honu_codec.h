@@ -30,6 +30,24 @@
  *     status arrays using the same enum.
  *   - The library is gfx950-only; it fails loudly (HONU_E_NO_DEVICE) when no
  *     gfx950 device is present. There is no CPU fallback.
+ *   - What a call stores, to the byte: the ranges [off[i], off[i+1]) of the
+ *     records it completes (status HONU_OK after the call); the first n rows,
+ *     infos, sizes / offsets (n + 1 where stated) and statuses; the table
+ *     entries of the records that fit their table; the payload ranges
+ *     [data_off, data_off + data_len) it reports with data_status HONU_OK;
+ *     and its totals (3 x u64 = 24 bytes, 8 for honu_decode_data). It never
+ *     stores in the range of a record that failed or that it was told to skip
+ *     (a status other than HONU_OK on entry), at or past a capacity (out_cap,
+ *     acl_cap, regions_cap, data_cap: a record or payload that does not fit
+ *     is not stored in part), in the data arena's 16-byte alignment gaps or
+ *     behind its last payload, in a neighbouring record's bytes of a shared
+ *     16- or 64-byte chunk, or anywhere before or behind a buffer. The
+ *     encode calls, honu_marshal_batch, honu_decode_batch and
+ *     honu_exclusive_scan check their arguments (the alignments stated at
+ *     honu_ctx_create, n against max_records) before their first launch:
+ *     refused with HONU_E_ARG or HONU_E_WORKSPACE, they have stored nothing.
+ *     Outputs may therefore lie back to back with memory the caller still
+ *     uses, and a result does not depend on where an arena lies.
  */
 #ifndef HONU_CODEC_H
 #define HONU_CODEC_H
@@ -332,8 +350,15 @@ int32_t honu_encode_sizes(honu_ctx *ctx, const honu_meta *d_meta, uint64_t var_l
                           uint64_t regions_len, const uint64_t *d_payload_off, uint64_t n,
                           uint64_t *d_sizes, int32_t *d_status, void *stream);
 
-/* Exclusive prefix sum: d_out[i] = sum(d_in[0..i)), d_out[n] = total.
- * d_out must hold n+1 values and may alias d_in only if equal. */
+/* Exclusive prefix sum: d_out[i] = sum(d_in[0..i)), d_out[n] = total
+ * (d_out[0] = 0 for n == 0). d_out must hold n+1 values and may alias d_in
+ * only if equal. Exact in uint64 arithmetic (modulo 2^64, as a serial sum)
+ * for up to 2^33 rows: the words that carry a tile's sum to the tiles after
+ * it hold 43 value bits, so the sum travels as three limbs. (The decode's
+ * internal three-column scans carry whole sums: table entries and data-arena
+ * bytes of one batch, exact while each total stays below 2^43 = 8 TiB.)
+ * n above the context's max_records returns HONU_E_WORKSPACE and stores
+ * nothing. */
 int32_t honu_exclusive_scan(honu_ctx *ctx, const uint64_t *d_in, uint64_t n, uint64_t *d_out,
                             void *stream);
 

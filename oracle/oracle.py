@@ -90,8 +90,17 @@ def size_bound(which: int, row) -> int:
     return load().oracle_size_bound(which, _p(row))
 
 
-def marshal_batch(hb):
-    """(records arena, out_off[n+1], status[n]) for a honu_amd.metadata.HostBatch."""
+POISON = 0xEE  # what the untrimmed buffers of a call with a capacity hold where nothing was stored
+
+
+def marshal_batch(hb, out_cap=None):
+    """(records arena, out_off[n+1], status[n]) for a honu_amd.metadata.HostBatch.
+
+    out_cap (None: the batch's own total): the capacity handed to
+    oracle_marshal_batch, whose records ending past it get HONU_ERR_CAPACITY.
+    With a capacity given the arena comes back untrimmed (the batch's total
+    bytes, POISON where nothing was stored), so a caller sees what lies at
+    and past it."""
     lib = load()
     n = len(hb.meta)
     out_off = np.zeros(n + 1, np.uint64)
@@ -100,11 +109,15 @@ def marshal_batch(hb):
                              _p(hb.regions), len(hb.regions), _p(hb.payload), _p(hb.payload_off),
                              n, None, 0, _p(out_off), _p(status))
     total = int(out_off[n])
-    out = np.zeros(max(total, 1), np.uint8)
+    if out_cap is None:
+        out = np.zeros(max(total, 1), np.uint8)
+    else:
+        out = np.full(max(total, int(out_cap), 1), POISON, np.uint8)
     lib.oracle_marshal_batch(_p(hb.meta), _p(hb.var), len(hb.var), _p(hb.acl), len(hb.acl),
                              _p(hb.regions), len(hb.regions), _p(hb.payload), _p(hb.payload_off),
-                             n, _p(out), total, _p(out_off), _p(status))
-    return out[:total], out_off, status
+                             n, _p(out), total if out_cap is None else int(out_cap), _p(out_off),
+                             _p(status))
+    return (out[:total] if out_cap is None else out), out_off, status
 
 
 def forms(acl_inplace: bool = True, regions_inplace: bool = True) -> int:
@@ -113,7 +126,8 @@ def forms(acl_inplace: bool = True, regions_inplace: bool = True) -> int:
 
 
 def decode_batch(rec: np.ndarray, rec_off: np.ndarray, materialize: bool = False,
-                 acl_inplace: bool = True, regions_inplace: bool = True):
+                 acl_inplace: bool = True, regions_inplace: bool = True,
+                 acl_cap=None, regions_cap=None, data_cap=None):
     """(meta rows, info, acl table, region table, data arena | None, totals[3]).
 
     acl_inplace (the product's default, context param "acl_inplace"): an ACL
@@ -121,7 +135,15 @@ def decode_batch(rec: np.ndarray, rec_off: np.ndarray, materialize: bool = False
     acl_off absolute in `rec`), only lists with a nil entry in the table.
     regions_inplace (the default, context param "regions_inplace"): every
     non-empty region list comes back in place (HONU_REGIONS_INPLACE,
-    regions_off absolute in `rec`), the region table stays empty."""
+    regions_off absolute in `rec`), the region table stays empty.
+
+    acl_cap, regions_cap (table entries), data_cap (bytes; only with
+    materialize): the capacities handed to oracle_decode_batch instead of
+    buffers no batch can fill; the records that do not fit get
+    HONU_ERR_CAPACITY and totals still report what the batch needs. With any
+    of them given the tables and the data arena come back untrimmed (each at
+    least as long as its capacity and as the batch needs, POISON bytes where
+    nothing was stored), so a caller sees what lies at and past a capacity."""
     from honu_amd.metadata import ACL_DTYPE, INFO_DTYPE, META_DTYPE
     lib = load()
     n = len(rec_off) - 1
@@ -132,13 +154,28 @@ def decode_batch(rec: np.ndarray, rec_off: np.ndarray, materialize: bool = False
     nbytes = int(rec_off[-1]) if n >= 0 else 0
     meta = np.zeros(max(n, 1), META_DTYPE)
     info = np.zeros(max(n, 1), INFO_DTYPE)
-    acl = np.zeros(nbytes + 1, ACL_DTYPE)  # lazily zeroed; a nil entry is 1 byte
-    reg = np.zeros(nbytes + 1, np.uint32)
-    data = np.zeros(nbytes + 16 * n + 16, np.uint8) if materialize else None
+    capped = not (acl_cap is None and regions_cap is None and data_cap is None)
+    if data_cap is not None and not materialize:
+        raise ValueError("data_cap needs materialize")
+
+    def buf(count, cap, dtype):  # lazily zeroed; a nil entry is 1 byte of its record
+        if not capped:
+            return np.zeros(count, dtype)
+        a = np.empty(max(count, int(cap or 0) + 1), dtype)
+        a.view(np.uint8)[:] = POISON
+        return a
+
+    acl = buf(nbytes + 1, acl_cap, ACL_DTYPE)
+    reg = buf(nbytes + 1, regions_cap, np.uint32)
+    data = buf(nbytes + 16 * n + 16, data_cap, np.uint8) if materialize else None
     totals = np.zeros(3, np.uint64)
-    lib.oracle_decode_batch(_p(rec), _p(rec_off), n, _p(meta), _p(info), _p(acl), len(acl),
-                            _p(reg), len(reg), _p(data), 0 if data is None else len(data),
+    lib.oracle_decode_batch(_p(rec), _p(rec_off), n, _p(meta), _p(info), _p(acl),
+                            len(acl) if acl_cap is None else int(acl_cap), _p(reg),
+                            len(reg) if regions_cap is None else int(regions_cap), _p(data),
+                            0 if data is None else (len(data) if data_cap is None else int(data_cap)),
                             _p(totals), forms(acl_inplace, regions_inplace))
+    if capped:
+        return meta[:n], info[:n], acl, reg, data, totals
     return (meta[:n], info[:n], acl[: int(totals[0])], reg[: int(totals[1])],
             None if data is None else data[: int(totals[2])], totals)
 

@@ -169,10 +169,10 @@ def test_put_feed_single_records_and_errors(oracle_lib):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    from test_gpu_parity import _odd_metas
+    from corpora import odd_metas
     from honu_amd.feed import PutFeed
     from honu_amd.metadata import pack_batch
-    metas, datas = _odd_metas(seed=12, n=36)
+    metas, datas = odd_metas(seed=12, n=36)
     metas.append(None)
     datas.append(b"x")
     feed = PutFeed(0, batch_records=64, batch_bytes=4 << 20)

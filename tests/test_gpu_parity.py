@@ -16,7 +16,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-from corpora import malformed_corpus, mutant_corpus, random_metas  # noqa: E402
+import guards  # noqa: E402
+from corpora import malformed_corpus, mutant_corpus, odd_metas, random_metas  # noqa: E402
 from fixtures import load_object_fixture, py_uvarint  # noqa: E402
 from honu_amd import object as hobj  # noqa: E402
 from honu_amd.metadata import META_DTYPE, normalize, pack_batch, unpack_row  # noqa: E402
@@ -59,18 +60,48 @@ def dev(a, codec):
     return hobj._dev_bytes(np.ascontiguousarray(a), codec.torch_device)
 
 
+POISON_FILL = 0xFF  # of guards.guarded: what an output byte holds until the call stores it
+
+
+def poisoned(codec, nbytes):
+    """An output buffer that holds the guard pattern instead of whatever the
+    caching allocator's last user left there: the seven configurations of the
+    `codec` fixture run the same batches with the same sizes one after the
+    other, so a torch.empty output often starts out holding the right bytes."""
+    return guards.guarded(max(int(nbytes), 16), fill=POISON_FILL, device=codec.torch_device)
+
+
 def gpu_marshal(codec, hb):
-    r = codec.marshal(hobj.DeviceBatch.from_host(hb, codec.torch_device))
+    """Codec.marshal (sizes, scan, total, honu_marshal_batch) with every
+    output poisoned first."""
+    b = hobj.DeviceBatch.from_host(hb, codec.torch_device)
+    out_off, status = poisoned(codec, 8 * (b.n + 1)), poisoned(codec, 4 * b.n)
+    codec.encode_sizes(b, out_off, status)
+    codec.scan(out_off, b.n, out_off)
+    total = int(out_off.view(torch.int64)[b.n].item())
+    out_off2, status2, out = poisoned(codec, 8 * (b.n + 1)), poisoned(codec, 4 * b.n), poisoned(codec, total)
+    codec.marshal_into(b, out, total, out_off2, status2)
     torch.cuda.synchronize()
-    return r.host()
+    return hobj.EncodeResult(out, out_off2, status2, b.n).host()
 
 
 def gpu_decode(codec, rec, off, materialize=False):
+    """Codec.decode (honu_decode_batch, tables and data arena sized by the
+    records' bytes) with every output poisoned first."""
+    L = hobj._lib
     n = len(off) - 1
-    d = codec.decode(dev(rec if len(rec) else np.zeros(1, np.uint8), codec), dev(off, codec), n,
-                     materialize=materialize, rec_bytes=int(off[-1]))
+    d_rec, d_off = dev(rec if len(rec) else np.zeros(1, np.uint8), codec), dev(off, codec)
+    rec_bytes = int(off[-1])
+    acl_cap = regions_cap = rec_bytes  # every ACL entry / region takes >= 1 byte of its record
+    data_cap = rec_bytes + 16 * n if materialize else 0
+    meta, info, totals = poisoned(codec, 352 * n), poisoned(codec, 32 * n), poisoned(codec, 32)
+    acl, reg = poisoned(codec, 20 * acl_cap), poisoned(codec, 4 * regions_cap)
+    data = poisoned(codec, data_cap) if materialize else None
+    L.check(codec.lib.honu_decode_batch(
+        codec.ctx, L.ptr(d_rec), L.ptr(d_off), n, L.ptr(meta), L.ptr(info), L.ptr(acl), acl_cap,
+        L.ptr(reg), regions_cap, L.ptr(data), data_cap, L.ptr(totals), codec.stream), "honu_decode_batch")
     torch.cuda.synchronize()
-    return d.host()
+    return hobj.DecodeResult(meta, info, acl, reg, data, totals, n).host()
 
 
 def assert_decode_equal(oracle_lib, codec, rec, off, materialize=False):
@@ -285,46 +316,8 @@ def test_full_size_property_large(codec, oracle_lib):
         assert out[int(goff[i]):int(goff[i + 1])].tobytes() == oout[int(ooff[i]):int(ooff[i + 1])].tobytes()
 
 
-def _odd_metas(seed=11, n=48):
-    """Records outside the generator's envelope: tails beyond one 2 KiB LDS
-    window (long frames, hundreds of ACL entries), nil ACL entries, more than
-    8 regions, multi-byte region varints, empty and nil lists."""
-    from honu_amd.metadata import (AccessControl, Compression, Encryption, Metadata, Publisher,
-                                   Scalar, SchemaVersion, Version)
-    rng = np.random.default_rng(seed)
-    metas, datas = [], []
-    for i in range(n):
-        kind = i % 6
-        nacl = [0, 3, 130, 300, 17, 64][kind]
-        acl = None if nacl == 0 else [
-            None if (kind in (1, 3, 4) and j % 7 == 3) else
-            AccessControl(rng.bytes(16), int(rng.integers(0, 256))) for j in range(nacl)]
-        regs = [int(x) for x in rng.integers(0, [2**7, 2**14, 2**21, 2**32, 2**32, 2**10][kind],
-                                              [0, 5, 9, 40, 8, 12][kind])]
-        sig = rng.bytes([0, 32, 5000, 300, 2100, 1][kind])
-        m = Metadata(
-            ObjectID=rng.bytes(16), CollectionID=rng.bytes(16),
-            Version=Version(Scalar(int(rng.integers(0, 2**32)), int(rng.integers(0, 2**63))),
-                            int(rng.integers(0, 2**32)), Scalar(7, 9) if kind % 2 else None,
-                            bool(kind & 2), int(rng.integers(-2**62, 2**62))),
-            Schema=SchemaVersion("S" * [0, 3, 700, 20, 5, 1][kind], 1, 2**20, 3) if kind else None,
-            MIME="m" * [0, 10, 3000, 17, 40, 2][kind], Owner=rng.bytes(16), Group=rng.bytes(16),
-            Permissions=int(rng.integers(0, 256)), ACL=acl,
-            WriteRegions=regs if kind != 0 else None,
-            Publisher=Publisher(rng.bytes(16), rng.bytes(16), rng.bytes(16),
-                                "UA" * [0, 5, 900, 1, 3, 7][kind]) if kind != 5 else None,
-            Encryption=Encryption("k" * 22, rng.bytes(32), rng.bytes(32), sig, 1, 2, 4)
-            if kind != 1 else None,
-            Compression=Compression(1, int(rng.integers(-5, 10))) if kind % 3 else None,
-            Flags=int(rng.integers(0, 256)), Created=int(rng.integers(0, 2**62)),
-            Modified=int(rng.integers(0, 2**62)))
-        metas.append(m)
-        datas.append(rng.bytes(int(rng.integers(0, 3000))) if i % 5 else None)
-    return metas, datas
-
-
 def test_long_tails_and_nil_entries_parity(codec, oracle_lib):
-    metas, datas = _odd_metas()
+    metas, datas = odd_metas()
     hb = pack_batch(metas, datas)
     out, off, st = gpu_marshal(codec, hb)
     oout, ooff, ost = oracle_lib.marshal_batch(hb)

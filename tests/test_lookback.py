@@ -28,6 +28,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import guards  # noqa: E402
 from honu_amd import object as hobj  # noqa: E402
 from honu_amd.workload import gen_host_batch  # noqa: E402
 
@@ -122,7 +123,8 @@ class _Dec:
         self.rec, self.off = _dev(rec, codec), _dev(off, codec)
         cap = int(off[-1])
         self.acl_cap = self.reg_cap = cap
-        e = codec._empty
+        # outputs hold the guard pattern, not a previous launch's (right) bytes
+        e = lambda nbytes: guards.guarded(max(nbytes, 16), fill=0xFF, device=codec.torch_device)  # noqa: E731
         self.meta, self.info, self.tot = e(352 * self.n), e(32 * self.n), e(32)
         self.acl, self.reg = e(20 * cap), e(4 * cap)
 
