@@ -16,6 +16,8 @@
 //
 //	object.Marshal            object.go:24-45  -> (*Codec).MarshalBatch
 //	(Object).Metadata / Data  object.go:66-99  -> (*Codec).DecodeBatch
+//	sort.Sort(keys.Keys)      keys/keys.go:126-130 -> (*Codec).SortKeys
+//	object version ranges     keys/keys.go:73-92   -> (*Codec).KeyObjects
 package object
 
 /*
@@ -611,4 +613,113 @@ func unflatten(r *C.honu_meta, arena []byte, acl []C.honu_acl, regs []uint32) *m
 			Level: int64(r.compression_level)}
 	}
 	return m
+}
+
+// KeyOrder is the result of SortKeys: the order on the host, and the device
+// buffers KeyObjects reads (the key column, the order, the valid count and
+// the workspace both calls share). Free releases them.
+//
+// UNCOMPILED, like the rest of this file. The two calls are exercised on the
+// GPU from Python (tests/test_gpu_sort.py), graph capture included.
+type KeyOrder struct {
+	Order []uint32 // record indices: [0, Valid) in bytes.Compare order of their keys, then the rest
+	Valid uint64   // keys of the right size (the others sort last, in index order)
+
+	n                        uint64
+	keys, order, valid, work devBuf
+	workBytes                uint64
+}
+
+func (o *KeyOrder) Free() {
+	for _, d := range []devBuf{o.keys, o.order, o.valid, o.work} {
+		d.free()
+	}
+}
+
+// SortKeys is sort.Sort(keys.Keys) (keys/keys.go:126-130: Less is
+// bytes.Compare < 0) on the GPU, made stable: equal keys keep their index
+// order. It does not move ks; it returns the order. A key that is not 29
+// bytes long takes no part (status HONU_ERR_MALFORMED) and sorts last.
+func (c *Codec) SortKeys(ks [][]byte) (*KeyOrder, error) {
+	n := uint64(len(ks))
+	hKeys, hSt := pinned(uintptr(C.HONU_KEY_LEN*n)), pinned(uintptr(4*n))
+	defer hKeys.free()
+	defer hSt.free()
+	col, st := hKeys.bytes(), unsafe.Slice((*C.int32_t)(hSt.p), n)
+	for i, k := range ks {
+		if len(k) == C.HONU_KEY_LEN {
+			copy(col[C.HONU_KEY_LEN*i:], k)
+			st[i] = C.HONU_OK
+		} else {
+			st[i] = C.HONU_ERR_MALFORMED
+		}
+	}
+	o := &KeyOrder{n: n, workBytes: uint64(C.honu_sort_keys_workspace(C.uint64_t(n)))}
+	o.keys, o.order, o.valid = device(hKeys.n), device(uintptr(4*n)), device(8)
+	o.work = device(uintptr(o.workBytes)) // hipMalloc: 256-byte aligned
+	dSt := device(hSt.n)
+	defer dSt.free()
+	hOrder, hValid := pinned(uintptr(4*n)), pinned(8)
+	defer hOrder.free()
+	defer hValid.free()
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(o.keys.p, hKeys.p, C.uint64_t(hKeys.n), c.stream),
+		C.honu_memcpy_h2d(dSt.p, hSt.p, C.uint64_t(hSt.n), c.stream),
+		C.honu_sort_keys(c.ctx, (*C.uint8_t)(o.keys.p), (*C.int32_t)(dSt.p), C.uint64_t(n),
+			(*C.uint32_t)(o.order.p), nil, (*C.uint64_t)(o.valid.p), o.work.p, C.uint64_t(o.workBytes), c.stream),
+		C.honu_memcpy_d2h(hOrder.p, o.order.p, C.uint64_t(4*n), c.stream),
+		C.honu_memcpy_d2h(hValid.p, o.valid.p, 8, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_sort_keys", s); err != nil {
+			o.Free()
+			return nil, err
+		}
+	}
+	o.Order = append([]uint32(nil), unsafe.Slice((*uint32)(hOrder.p), n)...)
+	o.Valid = *(*uint64)(hValid.p)
+	return o, nil
+}
+
+// KeyObjects cuts a sorted order into objects: what a read of "the latest
+// version ... or all versions related to the object" ranges over
+// (keys.go:40-41), [ObjectPrefix, ObjectLimit) (keys.go:73-92). Object j has
+// the versions o.Order[offsets[j]:offsets[j+1]], oldest first by
+// lamport.Compare (lamport/scalar.go:50-78), and latest[j] is the index of its
+// newest. Groups are by equality of the 17-byte prefix (ObjectLimit's
+// limit[16]++ wraps for an ObjectID ending in 0xff; that is not reproduced).
+func (c *Codec) KeyObjects(o *KeyOrder) (offsets []uint64, latest []uint32, err error) {
+	n := o.n
+	dOff, dLatest, dObjects := device(uintptr(8*(n+1))), device(uintptr(4*n)), device(8)
+	defer dOff.free()
+	defer dLatest.free()
+	defer dObjects.free()
+	hOff, hLatest, hObjects := pinned(uintptr(8*(n+1))), pinned(uintptr(4*n)), pinned(8)
+	defer hOff.free()
+	defer hLatest.free()
+	defer hObjects.free()
+	for _, s := range []C.int32_t{
+		C.honu_key_objects(c.ctx, (*C.uint8_t)(o.keys.p), (*C.uint32_t)(o.order.p), (*C.uint64_t)(o.valid.p),
+			C.uint64_t(n), (*C.uint64_t)(dOff.p), (*C.uint32_t)(dLatest.p), (*C.uint64_t)(dObjects.p),
+			o.work.p, C.uint64_t(o.workBytes), c.stream),
+		C.honu_memcpy_d2h(hObjects.p, dObjects.p, 8, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_objects", s); err != nil {
+			return nil, nil, err
+		}
+	}
+	objects := *(*uint64)(hObjects.p)
+	for _, s := range []C.int32_t{ // only what was written: objects + 1 offsets, objects indices
+		C.honu_memcpy_d2h(hOff.p, dOff.p, C.uint64_t(8*(objects+1)), c.stream),
+		C.honu_memcpy_d2h(hLatest.p, dLatest.p, C.uint64_t(4*objects), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("download", s); err != nil {
+			return nil, nil, err
+		}
+	}
+	offsets = append([]uint64(nil), unsafe.Slice((*uint64)(hOff.p), objects+1)...)
+	latest = append([]uint32(nil), unsafe.Slice((*uint32)(hLatest.p), objects)...)
+	return offsets, latest, nil
 }

@@ -50,6 +50,9 @@ _PROTOS = {
     "honu_decode_batch": (I32, [P, P, P, U64, P, P, P, U64, P, U64, P, U64, P, P]),
     "honu_decode_records": (I32, [P, P, P, U64, P, P, P, U64, P, U64, I32, U64, P, P]),
     "honu_decode_keys": (I32, [P, P, P, U64, P, P, P]),
+    "honu_sort_keys_workspace": (U64, [U64]),
+    "honu_sort_keys": (I32, [P, P, P, U64, P, P, P, P, U64, P]),
+    "honu_key_objects": (I32, [P, P, P, P, U64, P, P, P, P, U64, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -376,6 +376,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "encode_variant")) *value = ctx->geom.encode_variant;
     else if (!strcmp(name, "record_variant")) *value = ctx->geom.record_variant;
     else if (!strcmp(name, "walk_flag_checks")) *value = decode_walk_flag_checks();  // read only: the build's
+    else if (!strcmp(name, "sort_tile")) *value = sort_tile();  // read only: keys per workgroup per sort pass
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -752,6 +753,49 @@ int32_t honu_decode_keys(honu_ctx *ctx, const honu_meta *d_meta, const honu_reco
     if (!ctx) return arg_fail("ctx");
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_decode_keys(ctx->geom, d_meta, d_info, n, d_keys, d_key_status,
+                              (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// key order (keys/keys.go:126-130) and version ranges (keys.go:73-92)
+// ---------------------------------------------------------------------------
+uint64_t honu_sort_keys_workspace(uint64_t n) { return sort_workspace_bytes(n); }
+
+// the checks the two calls share; 0 or the refusal
+static int32_t sort_args(honu_ctx *ctx, uint64_t n, const void *d_work, uint64_t work_bytes) {
+    if (!ctx) return arg_fail("ctx");
+    if (n > ctx->max_n || n > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    if (!d_work || !aligned(d_work, 256)) return arg_fail("workspace must be non-null and 256-byte aligned");
+    if (work_bytes < sort_workspace_bytes(n)) return arg_fail("workspace smaller than honu_sort_keys_workspace(n)");
+    return HONU_OK;
+}
+
+int32_t honu_sort_keys(honu_ctx *ctx, const uint8_t *d_keys, const int32_t *d_key_status, uint64_t n,
+                       uint32_t *d_order, uint8_t *d_sorted, uint64_t *d_valid, void *d_work,
+                       uint64_t work_bytes, void *stream) {
+    const int32_t st = sort_args(ctx, n, d_work, work_bytes);
+    if (st) return st;
+    if (!d_valid || (n && (!d_keys || !d_order))) return arg_fail("null pointer");
+    if (!aligned(d_key_status, 4) || !aligned(d_order, 4) || !aligned(d_valid, 8))
+        return arg_fail("status and order 4-byte / valid count 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_sort_keys(d_keys, d_key_status, n, d_order, d_sorted, d_valid, d_work, ctx->scan,
+                            ctx->max_n, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+int32_t honu_key_objects(honu_ctx *ctx, const uint8_t *d_keys, const uint32_t *d_order,
+                         const uint64_t *d_valid, uint64_t n, uint64_t *d_obj_off, uint32_t *d_latest,
+                         uint64_t *d_objects, void *d_work, uint64_t work_bytes, void *stream) {
+    const int32_t st = sort_args(ctx, n, d_work, work_bytes);
+    if (st) return st;
+    if (!d_valid || !d_obj_off || !d_objects || (n && (!d_keys || !d_order))) return arg_fail("null pointer");
+    if (!aligned(d_order, 4) || !aligned(d_latest, 4) || !aligned(d_valid, 8) || !aligned(d_obj_off, 8) ||
+        !aligned(d_objects, 8))
+        return arg_fail("order and latest 4-byte / counts and offsets 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_objects(d_keys, d_order, d_valid, n, d_obj_off, d_latest, d_objects, d_work, ctx->scan,
                               (hipStream_t)stream));
     return HONU_OK;
 }

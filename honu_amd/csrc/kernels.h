@@ -229,6 +229,28 @@ uint64_t scan_status_words(uint64_t n);
 hipError_t launch_scan(const uint64_t *in, uint64_t n, int K, uint64_t *out, uint64_t *totals,
                        const ScanState &S, hipStream_t s);
 
+// sort.hip: sort.Sort(keys.Keys) (keys.go:126-130) and the objects' version
+// ranges (keys.go:73-92). The caller's workspace, carved: the plan words, the
+// two sides of packed keys (32 bytes each) and indices, the one scan column
+// (n + 1 rows) and the digit-major count table (256 rows per tile).
+struct SortWork {
+    uint32_t *plan;
+    u32x4 *key[2];
+    uint32_t *idx[2];
+    uint64_t *col;
+    uint64_t *table;
+};
+uint32_t sort_tile();
+uint64_t sort_workspace_bytes(uint64_t n);
+SortWork sort_carve(void *work, uint64_t n);
+// scan_rows: the rows the context's scan state covers (its max_records)
+hipError_t launch_sort_keys(const uint8_t *keys, const int32_t *status, uint64_t n, uint32_t *order,
+                            uint8_t *sorted, uint64_t *valid, void *work, const ScanState &S,
+                            uint64_t scan_rows, hipStream_t s);
+hipError_t launch_key_objects(const uint8_t *keys, const uint32_t *order, const uint64_t *valid, uint64_t n,
+                              uint64_t *obj_off, uint32_t *latest, uint64_t *objects, void *work,
+                              const ScanState &S, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

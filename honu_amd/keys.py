@@ -1,0 +1,97 @@
+"""Host mirror of pkg/store/keys: the 29-byte object storage key.
+
+A key is keyVersion | ObjectID (16) | BE64(VID) | BE32(PID) (keys/keys.go:27-51):
+the version is serialized big endian "to maintain lexicographic sorting"
+(keys.go:35-36), so bytes.Compare order of the keys of one object is
+lamport.Compare order of its versions (lamport/scalar.go:50-78: VID, then
+PID). Keys are bytes; the functions take what Go's methods take as receiver.
+sort() is the host statement of Keys (keys.go:126-130); the batch form on the
+GPU is Codec.sort_keys / Codec.key_objects (object.py, honu_sort_keys and
+honu_key_objects in include/honu_codec.h).
+"""
+from __future__ import annotations
+
+from typing import Iterable, List, Optional
+
+from .metadata import Scalar
+
+KEY_SIZE = 29       # keys.go:14
+KEY_VERSION = 0x01  # keys.go:18
+PREFIX_SIZE = 17    # keyVersion + ObjectID: ObjectPrefix (keys.go:74-79)
+
+
+class KeyError_(Exception):
+    pass
+
+
+class ErrBadVersion(KeyError_):  # keys.go:22
+    def __init__(self):
+        super().__init__("key is malformed: cannot decode specified version")
+
+
+class ErrBadSize(KeyError_):  # keys.go:23
+    def __init__(self):
+        super().__init__("key is malformed: incorrect size")
+
+
+class ErrMalformed(KeyError_):  # keys.go:24
+    def __init__(self):
+        super().__init__("key is malformed: cannot parse version components")
+
+
+def new(oid: bytes, vers: Optional[Scalar] = None) -> bytes:
+    """keys.New (keys.go:42-51). A None version leaves the object prefix
+    followed by zeros: the key that sorts before every version of the object."""
+    oid = bytes(oid)
+    if len(oid) != 16:
+        raise ValueError("an object ID is 16 bytes")
+    key = bytearray(KEY_SIZE)
+    key[0] = KEY_VERSION
+    key[1:17] = oid
+    if vers is not None:
+        key[17:25] = int(vers.VID).to_bytes(8, "big")
+        key[25:29] = int(vers.PID).to_bytes(4, "big")
+    return bytes(key)
+
+
+def check(key: bytes) -> None:
+    """Key.Check (keys.go:110-120), raising where Go returns the error."""
+    if len(key) != KEY_SIZE:
+        raise ErrBadSize()
+    if key[0] != KEY_VERSION:
+        raise ErrBadVersion()
+
+
+def object_id(key: bytes) -> bytes:  # keys.go:54-59 (Go panics with Check's error)
+    check(key)
+    return bytes(key[1:17])
+
+
+def version(key: bytes) -> Scalar:  # keys.go:63-71
+    check(key)
+    return Scalar(PID=int.from_bytes(key[25:29], "big"), VID=int.from_bytes(key[17:25], "big"))
+
+
+def object_prefix(key: bytes) -> bytes:  # keys.go:74-79
+    check(key)
+    return bytes(key[0:PREFIX_SIZE])
+
+
+def object_limit(key: bytes) -> bytes:
+    """Key.ObjectLimit (keys.go:84-92): the prefix with its last byte
+    incremented, as Go's limit[16]++ does: a last byte of 0xff wraps to 0."""
+    check(key)
+    limit = bytearray(key[0:PREFIX_SIZE])
+    limit[16] = (limit[16] + 1) & 0xFF
+    return bytes(limit)
+
+
+def has_version(key: bytes) -> bool:  # keys.go:97-108
+    check(key)
+    return any(key[PREFIX_SIZE:KEY_SIZE])
+
+
+def sort(keys: Iterable[bytes]) -> List[bytes]:
+    """sort.Sort(keys.Keys) (keys.go:126-130): ascending bytes.Compare, which
+    is Python's order of bytes. Stable, which sort.Sort does not promise."""
+    return sorted(bytes(k) for k in keys)

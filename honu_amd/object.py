@@ -276,6 +276,47 @@ class Codec:
                    "honu_decode_keys")
         return keys, st
 
+    # ---- key order ------------------------------------------------------
+    def sort_workspace(self, n: int):
+        """The workspace of sort_keys / key_objects for n keys (honu_sort_keys_workspace)."""
+        nbytes = int(self.lib.honu_sort_keys_workspace(n))
+        return self._empty(nbytes), nbytes
+
+    def sort_keys(self, keys, key_status=None, n: Optional[int] = None, want_sorted: bool = False):
+        """sort.Sort(keys.Keys) (keys/keys.go:126-130), stable, over the device
+        key column of Codec.keys: (order, n record indices as an int32 view of
+        the uint32 column; sorted column or None; valid count, one int64), all
+        on the device. Keys whose status is not OK follow the valid ones, in
+        index order."""
+        if n is None:
+            n = keys.numel() // 29
+        order = self._empty(4 * n)
+        out = self._empty(29 * n) if want_sorted else None
+        valid = self._empty(8)
+        work, work_bytes = self.sort_workspace(n)
+        _lib.check(self.lib.honu_sort_keys(
+            self.ctx, _lib.ptr(keys), _lib.ptr(key_status), n, _lib.ptr(order), _lib.ptr(out),
+            _lib.ptr(valid), _lib.ptr(work), work_bytes, self.stream), "honu_sort_keys")
+        return order[:4 * n].view(_torch().int32), out, valid[:8].view(_torch().int64)
+
+    def key_objects(self, keys, order, valid):
+        """The objects of a sorted column (keys.go:73-92) from sort_keys' order
+        and valid count, which stay on the device: (offsets uint64[n+1] of
+        which objects + 1 are set, latest record index per object uint32[n] of
+        which `objects` are set, object count uint64[1])."""
+        n = order.numel()
+        obj_off = self._empty(8 * (n + 1))
+        latest = self._empty(4 * n)
+        objects = self._empty(8)
+        work, work_bytes = self.sort_workspace(n)
+        _lib.check(self.lib.honu_key_objects(
+            self.ctx, _lib.ptr(keys), _lib.ptr(order), _lib.ptr(valid), n, _lib.ptr(obj_off),
+            _lib.ptr(latest), _lib.ptr(objects), _lib.ptr(work), work_bytes, self.stream),
+            "honu_key_objects")
+        torch = _torch()
+        return (obj_off[:8 * (n + 1)].view(torch.int64), latest[:4 * n].view(torch.int32),
+                objects[:8].view(torch.int64))
+
 
 _default: Optional[Codec] = None
 

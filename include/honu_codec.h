@@ -16,6 +16,8 @@
  *   Object.Tombstone()          object.go:103-112        results land in honu_record_info
  *   Object.StorageVersion()     object.go:47-52
  *   Object.Key()                object.go:57-64        honu_decode_keys (29-byte keys.Key column)
+ *   sort.Sort(keys.Keys)        keys/keys.go:126-130   honu_sort_keys (stable order of the column)
+ *   an object's versions        keys/keys.go:73-92     honu_key_objects (ranges of the order, latest)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -521,6 +523,53 @@ int32_t honu_decode_data_copy(honu_ctx *ctx, const uint8_t *d_rec, uint64_t n,
  * when the decoded Version is nil (metadata.go:54 dereferences it). */
 int32_t honu_decode_keys(honu_ctx *ctx, const honu_meta *d_meta, const honu_record_info *d_info,
                          uint64_t n, uint8_t *d_keys, int32_t *d_key_status, void *stream);
+
+/* Bytes of caller-owned device workspace that honu_sort_keys and
+ * honu_key_objects need for n keys (one workspace serves both): a multiple of
+ * 256, monotonic in n, at most 96 n + 2^20. The workspace itself must be
+ * 256-byte aligned (hipMalloc gives that). The context's own allocations do
+ * not grow with these calls. Needs no device. */
+uint64_t honu_sort_keys_workspace(uint64_t n);
+
+/* sort.Sort(keys.Keys) (keys/keys.go:126-130: Less is bytes.Compare < 0),
+ * made deterministic: a stable sort of the key column honu_decode_keys writes
+ * (29 bytes per key at d_keys + 29*i, any byte alignment) over all 29 bytes.
+ * Key i takes part when d_key_status is NULL or d_key_status[i] == HONU_OK.
+ * d_order[0, valid) receives the indices of the valid keys in ascending key
+ * order, equal keys in ascending index; d_order[valid, n) the other indices,
+ * ascending: always a permutation of 0..n-1. d_sorted (optional, 29 n bytes):
+ * row p is d_keys row d_order[p], for every p < n. d_valid[0] = valid. With
+ * n == 0 only d_valid[0] = 0 is written. Asynchronous on `stream`, no host
+ * synchronisation, replays from a captured graph; uses the context's scan
+ * state (one context per concurrent stream). Refusals, each storing nothing:
+ * HONU_E_WORKSPACE for n above honu_ctx_max_records or above 2^32 - 1;
+ * HONU_E_ARG for work_bytes below honu_sort_keys_workspace(n), a NULL or
+ * misaligned workspace, or NULL d_keys, d_order (n > 0) or d_valid.
+ * The get-only param "sort_tile" is the keys one workgroup takes per pass. */
+int32_t honu_sort_keys(honu_ctx *ctx, const uint8_t *d_keys, const int32_t *d_key_status,
+                       uint64_t n, uint32_t *d_order, uint8_t *d_sorted, uint64_t *d_valid,
+                       void *d_work, uint64_t work_bytes, void *stream);
+
+/* The objects of a sorted key column with their versions: what a read of
+ * "the latest version ... or all versions related to the object"
+ * (keys.go:40-41) ranges over, [ObjectPrefix, ObjectLimit) (keys.go:73-92).
+ * The positions p < d_valid[0] of d_order (both as honu_sort_keys wrote them;
+ * d_valid is read on the device, so the call follows the sort on the same
+ * stream with no host round trip) are cut where key[0:17] changes.
+ * d_obj_off (room for n + 1 values; objects + 1 are written): the versions of
+ * object j are d_order[d_obj_off[j], d_obj_off[j+1]), oldest first by
+ * lamport.Compare (lamport/scalar.go:50-78: VID, then PID), and
+ * d_obj_off[objects] = valid. d_latest (optional, room for n; `objects` are
+ * written): d_latest[j] = d_order[d_obj_off[j+1] - 1]. d_objects[0] =
+ * objects. Groups are by equality of the 17-byte prefix: ObjectLimit()'s
+ * limit[16]++ (keys.go:88-91) wraps for an object ID that ends in 0xff, which
+ * leaves the reference's own range empty there; that is not reproduced.
+ * Workspace, refusals and stream rules as honu_sort_keys (d_valid, d_obj_off
+ * and d_objects are required; d_keys and d_order when n > 0). */
+int32_t honu_key_objects(honu_ctx *ctx, const uint8_t *d_keys, const uint32_t *d_order,
+                         const uint64_t *d_valid, uint64_t n, uint64_t *d_obj_off,
+                         uint32_t *d_latest, uint64_t *d_objects,
+                         void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
