@@ -18,6 +18,7 @@
 //	(Object).Metadata / Data  object.go:66-99  -> (*Codec).DecodeBatch
 //	sort.Sort(keys.Keys)      keys/keys.go:126-130 -> (*Codec).SortKeys
 //	object version ranges     keys/keys.go:73-92   -> (*Codec).KeyObjects
+//	Cursor.Seek, Has, Exists  iterator/cursor.go:44-55, collection.go:47-65 -> (*Codec).SeekKeys, Has, Exists
 package object
 
 /*
@@ -625,13 +626,13 @@ type KeyOrder struct {
 	Order []uint32 // record indices: [0, Valid) in bytes.Compare order of their keys, then the rest
 	Valid uint64   // keys of the right size (the others sort last, in index order)
 
-	n                        uint64
-	keys, order, valid, work devBuf
+	n                                uint64
+	keys, order, sorted, valid, work devBuf // sorted: the column in order, which SeekKeys searches
 	workBytes                uint64
 }
 
 func (o *KeyOrder) Free() {
-	for _, d := range []devBuf{o.keys, o.order, o.valid, o.work} {
+	for _, d := range []devBuf{o.keys, o.order, o.sorted, o.valid, o.work} {
 		d.free()
 	}
 }
@@ -656,6 +657,7 @@ func (c *Codec) SortKeys(ks [][]byte) (*KeyOrder, error) {
 	}
 	o := &KeyOrder{n: n, workBytes: uint64(C.honu_sort_keys_workspace(C.uint64_t(n)))}
 	o.keys, o.order, o.valid = device(hKeys.n), device(uintptr(4*n)), device(8)
+	o.sorted = device(hKeys.n)
 	o.work = device(uintptr(o.workBytes)) // hipMalloc: 256-byte aligned
 	dSt := device(hSt.n)
 	defer dSt.free()
@@ -666,7 +668,8 @@ func (c *Codec) SortKeys(ks [][]byte) (*KeyOrder, error) {
 		C.honu_memcpy_h2d(o.keys.p, hKeys.p, C.uint64_t(hKeys.n), c.stream),
 		C.honu_memcpy_h2d(dSt.p, hSt.p, C.uint64_t(hSt.n), c.stream),
 		C.honu_sort_keys(c.ctx, (*C.uint8_t)(o.keys.p), (*C.int32_t)(dSt.p), C.uint64_t(n),
-			(*C.uint32_t)(o.order.p), nil, (*C.uint64_t)(o.valid.p), o.work.p, C.uint64_t(o.workBytes), c.stream),
+			(*C.uint32_t)(o.order.p), (*C.uint8_t)(o.sorted.p), (*C.uint64_t)(o.valid.p), o.work.p,
+			C.uint64_t(o.workBytes), c.stream),
 		C.honu_memcpy_d2h(hOrder.p, o.order.p, C.uint64_t(4*n), c.stream),
 		C.honu_memcpy_d2h(hValid.p, o.valid.p, 8, c.stream),
 		C.honu_stream_sync(c.stream),
@@ -722,4 +725,99 @@ func (c *Codec) KeyObjects(o *KeyOrder) (offsets []uint64, latest []uint32, err 
 	offsets = append([]uint64(nil), unsafe.Slice((*uint64)(hOff.p), objects+1)...)
 	latest = append([]uint32(nil), unsafe.Slice((*uint32)(hLatest.p), objects)...)
 	return offsets, latest, nil
+}
+
+// Seek is one row of SeekKeys: honu_seek (include/honu_codec.h).
+//
+// UNCOMPILED, like the rest of this file. honu_key_seek is exercised on the
+// GPU from Python (tests/test_gpu_key_seek.py), graph capture included.
+type Seek struct {
+	Pos, End      uint32 // Cursor.Seek's position in the sorted order; [Pos, End) are the probe's keys
+	First, Latest uint32 // o.Order[Pos], o.Order[End-1]: record indices (C.HONU_SEEK_NONE unless Found)
+	Flags         uint32 // C.HONU_SEEK_*
+}
+
+func (s Seek) Found() bool { return s.Flags&C.HONU_SEEK_FOUND != 0 }
+
+// SeekKeys is iterator.Cursor.Seek (iterator/cursor.go:44-55) for a batch of
+// probes over a sorted order: for probe q, the first position whose key is >=
+// probes[q] by bytes.Compare (o.Valid when there is none: Seek returns nil),
+// and the position past the last key that has probes[q] as prefix. Every probe
+// has the same length, 0..29: 29 a key, 17 an ObjectPrefix (keys.go:74-79), 16
+// a bare id as Collection.Has passes it. info (the decode's record info rows on
+// the device, or a zero devBuf) enables the two LIVE flags.
+func (c *Codec) SeekKeys(o *KeyOrder, probes [][]byte, info devBuf) ([]Seek, error) {
+	m := uint64(len(probes))
+	if m == 0 {
+		return nil, nil
+	}
+	plen := len(probes[0])
+	if plen > C.HONU_KEY_LEN {
+		return nil, fmt.Errorf("a probe is at most %d bytes", C.HONU_KEY_LEN)
+	}
+	hP, hOut := pinned(uintptr(C.HONU_KEY_LEN*m)), pinned(uintptr(uint64(C.honu_sizeof_seek())*m))
+	defer hP.free()
+	defer hOut.free()
+	col := hP.bytes()
+	for q, p := range probes {
+		if len(p) != plen {
+			return nil, fmt.Errorf("probe %d: %d bytes, the batch's probes have %d", q, len(p), plen)
+		}
+		copy(col[C.HONU_KEY_LEN*q:], p) // the row's other bytes are not compared
+	}
+	dP, dOut := device(hP.n), device(hOut.n)
+	defer dP.free()
+	defer dOut.free()
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(dP.p, hP.p, C.uint64_t(hP.n), c.stream),
+		C.honu_key_seek(c.ctx, (*C.uint8_t)(o.sorted.p), (*C.uint64_t)(o.valid.p), C.uint64_t(o.n),
+			(*C.uint8_t)(dP.p), nil, C.uint32_t(plen), C.uint64_t(m), (*C.uint32_t)(o.order.p),
+			(*C.honu_record_info)(info.p), (*C.honu_seek)(dOut.p), c.stream),
+		C.honu_memcpy_d2h(hOut.p, dOut.p, C.uint64_t(hOut.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_key_seek", s); err != nil {
+			return nil, err
+		}
+	}
+	rows := unsafe.Slice((*C.honu_seek)(hOut.p), m)
+	out := make([]Seek, m)
+	for q, r := range rows {
+		out[q] = Seek{uint32(r.pos), uint32(r.end), uint32(r.first), uint32(r.latest), uint32(r.flags)}
+	}
+	return out, nil
+}
+
+// Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&
+// bytes.HasPrefix(key, probe) of the key Seek lands on.
+func (c *Codec) Has(o *KeyOrder, probes [][]byte) ([]bool, error) {
+	rows, err := c.SeekKeys(o, probes, devBuf{})
+	if err != nil {
+		return nil, err
+	}
+	has := make([]bool, len(rows))
+	for q, r := range rows {
+		has[q] = r.Found()
+	}
+	return has, nil
+}
+
+// Exists is Collection.Exists (collection.go:55-65) for a batch. asWritten
+// reads the tombstone of the value at the Seek position, the object's lowest
+// version, as the reference's code does (collection.go:57-64); otherwise of the
+// latest version, as its comment documents (collection.go:53-54).
+func (c *Codec) Exists(o *KeyOrder, probes [][]byte, info devBuf, asWritten bool) ([]bool, error) {
+	rows, err := c.SeekKeys(o, probes, info)
+	if err != nil {
+		return nil, err
+	}
+	bit := uint32(C.HONU_SEEK_LATEST_LIVE)
+	if asWritten {
+		bit = C.HONU_SEEK_FIRST_LIVE
+	}
+	exists := make([]bool, len(rows))
+	for q, r := range rows {
+		exists[q] = r.Flags&bit != 0
+	}
+	return exists, nil
 }

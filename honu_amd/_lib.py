@@ -53,6 +53,8 @@ _PROTOS = {
     "honu_sort_keys_workspace": (U64, [U64]),
     "honu_sort_keys": (I32, [P, P, P, U64, P, P, P, P, U64, P]),
     "honu_key_objects": (I32, [P, P, P, P, U64, P, P, P, P, U64, P]),
+    "honu_sizeof_seek": (U64, []),
+    "honu_key_seek": (I32, [P, P, P, U64, P, P, C.c_uint32, U64, P, P, P, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

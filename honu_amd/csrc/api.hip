@@ -149,6 +149,7 @@ uint64_t honu_sizeof_acl(void) { return sizeof(honu_acl); }
 uint64_t honu_sizeof_collection(void) { return sizeof(honu_collection); }
 uint64_t honu_sizeof_index(void) { return sizeof(honu_index); }
 uint64_t honu_sizeof_record_info(void) { return sizeof(honu_record_info); }
+uint64_t honu_sizeof_seek(void) { return sizeof(honu_seek); }
 const char *honu_last_error(void) { return g_last_error; }
 
 const char *honu_status_string(int32_t st) {
@@ -352,6 +353,7 @@ int32_t honu_ctx_set_param(honu_ctx *ctx, const char *name, int64_t value) {
     else if (!strcmp(name, "record_variant") &&
              (value == 0 || value == 5 || value == 6))
         ctx->geom.record_variant = (int)value;
+    else if (!strcmp(name, "seek_variant") && value >= 0 && value <= 2) ctx->geom.seek_variant = (int)value;
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -377,6 +379,10 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "record_variant")) *value = ctx->geom.record_variant;
     else if (!strcmp(name, "walk_flag_checks")) *value = decode_walk_flag_checks();  // read only: the build's
     else if (!strcmp(name, "sort_tile")) *value = sort_tile();  // read only: keys per workgroup per sort pass
+    else if (!strcmp(name, "seek_variant")) *value = ctx->geom.seek_variant;
+    else if (!strcmp(name, "seek_fence")) *value = seek_fence();  // read only: keys of the fenced seek's LDS stage
+    else if (!strcmp(name, "seek_auto_probes")) *value = (int64_t)seek_auto_probes();  // read only: what
+    else if (!strcmp(name, "seek_auto_keys")) *value = (int64_t)seek_auto_keys();      // "seek_variant" 0 picks by
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -797,6 +803,28 @@ int32_t honu_key_objects(honu_ctx *ctx, const uint8_t *d_keys, const uint32_t *d
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_objects(d_keys, d_order, d_valid, n, d_obj_off, d_latest, d_objects, d_work, ctx->scan,
                               (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Cursor.Seek over the sorted column (iterator/cursor.go:44-55)
+// ---------------------------------------------------------------------------
+int32_t honu_key_seek(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_valid, uint64_t n,
+                      const uint8_t *d_probes, const int32_t *d_probe_status, uint32_t probe_len, uint64_t m,
+                      const uint32_t *d_order, const honu_record_info *d_info, honu_seek *d_out,
+                      void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    if (probe_len > HONU_KEY_LEN) return arg_fail("probe_len above 29");
+    if (!d_valid || (n && !d_sorted) || (m && (!d_probes || !d_out))) return arg_fail("null pointer");
+    if (d_info && !d_order) return arg_fail("d_info needs d_order");
+    if (!aligned(d_out, 4) || !aligned(d_order, 4) || !aligned(d_probe_status, 4) || !aligned(d_valid, 8) ||
+        !aligned(d_info, 8))
+        return arg_fail("rows, order and status 4-byte / valid count and record info 8-byte aligned");
+    if (m == 0) return HONU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_seek(ctx->geom.seek_variant, ctx->geom.num_cu, d_sorted, d_valid, n, d_probes,
+                           d_probe_status, probe_len, m, d_order, d_info, d_out, (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -105,6 +105,8 @@ struct LaunchGeom {
                             // records), 5 split decode, 6 single-launch decode
                             // at every size (the rejected one-record-per-wave /
                             // per-group / per-lane forms 1-4: DESIGN §3)
+    int seek_variant;       // honu_key_seek: 0 auto (by the probe and row counts), 1 the direct
+                            // binary search, 2 the fenced one (seek.hip)
     uint32_t *tile_map;     // sweep-form tile -> segment map (context scratch)
     uint64_t tile_map_cap;
     uint32_t *copy_tickets; // the copies' range-tail counters (copy.hip): in the context's
@@ -250,6 +252,15 @@ hipError_t launch_sort_keys(const uint8_t *keys, const int32_t *status, uint64_t
 hipError_t launch_key_objects(const uint8_t *keys, const uint32_t *order, const uint64_t *valid, uint64_t n,
                               uint64_t *obj_off, uint32_t *latest, uint64_t *objects, void *work,
                               const ScanState &S, hipStream_t s);
+
+// seek.hip: Cursor.Seek (iterator/cursor.go:44-55) for a batch of probes over
+// the sorted column. variant: 0 auto, 1 direct, 2 fenced (LaunchGeom::seek_variant)
+uint32_t seek_fence();
+uint64_t seek_auto_probes();  // variant 0 takes the direct form for fewer probes than this ...
+uint64_t seek_auto_keys();    // ... over more rows than this, the fenced form otherwise
+hipError_t launch_key_seek(int variant, int num_cu, const uint8_t *sorted, const uint64_t *valid, uint64_t n,
+                           const uint8_t *probes, const int32_t *pstatus, uint32_t probe_len, uint64_t m,
+                           const uint32_t *order, const honu_record_info *info, honu_seek *out, hipStream_t s);
 
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);

@@ -22,6 +22,7 @@
 // has more rows than the context's scan state is sized for), then a stable
 // scatter. No spin-wait of its own.
 #include "kernels.h"
+#include "keypack.h"
 
 namespace honu {
 
@@ -29,7 +30,6 @@ constexpr int SORT_ITEMS = 8;                               // keys per thread
 constexpr uint32_t SORT_TILE = HONU_BLOCK * SORT_ITEMS;     // keys per workgroup per pass
 constexpr uint32_t SORT_WAVE_KEYS = HONU_WAVE * SORT_ITEMS; // consecutive keys of one wave
 constexpr int SORT_DIGITS = 30;
-constexpr int SORT_KEY_WORDS = 8;
 // plan words (SortWork::plan): [d] pass d: bit 0 runs, bit 1 the side it reads;
 // [30] the side the sorted pairs end on; [32..39] the OR mask
 constexpr int PLAN_FINAL = 30, PLAN_MASK = 32, PLAN_WORDS = 64;
@@ -66,29 +66,6 @@ SortWork sort_carve(void *work, uint64_t n) {
 // which word of the packed key holds digit d, and the shift that brings it down
 HONU_HD uint32_t digit_word(int d) { return (uint32_t)(29 - d) >> 2; }
 HONU_HD uint32_t digit_shift(int d) { return (3u - ((uint32_t)(29 - d) & 3u)) * 8u; }
-
-// byte j (0..28) of a key loaded as its bytes [0,16) in a and [13,29) in b
-HONU_DEV uint32_t key_byte(const u32x4 &a, const u32x4 &b, int j) {
-    return j < 16 ? (a[j >> 2] >> (8 * (j & 3))) & 0xFFu : (b[(j - 13) >> 2] >> (8 * ((j - 13) & 3))) & 0xFFu;
-}
-
-// the packed form of the key at k (any byte address): two overlapping
-// 16-byte loads cover the 29 bytes and not one more
-HONU_DEV void pack_key(const uint8_t *k, bool valid, uint32_t w[SORT_KEY_WORDS]) {
-#pragma unroll
-    for (int i = 0; i < SORT_KEY_WORDS; i++) w[i] = 0;
-    if (!valid) {  // equal among themselves, so they keep their index order, and after every valid key
-        w[0] = 1u << 24;
-        return;
-    }
-    const u32x4 a = *reinterpret_cast<const u32x4u *>(k);
-    const u32x4 b = *reinterpret_cast<const u32x4u *>(k + 13);
-#pragma unroll
-    for (int j = 0; j < HONU_KEY_LEN; j++) {
-        const int pb = j + 1;  // packed byte
-        w[pb >> 2] |= key_byte(a, b, j) << (8 * (3 - (pb & 3)));
-    }
-}
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_sort_pack(const uint8_t *__restrict__ keys,
                                                           const int32_t *__restrict__ status, uint64_t n,

@@ -7,11 +7,15 @@ lamport.Compare order of its versions (lamport/scalar.go:50-78: VID, then
 PID). Keys are bytes; the functions take what Go's methods take as receiver.
 sort() is the host statement of Keys (keys.go:126-130); the batch form on the
 GPU is Codec.sort_keys / Codec.key_objects (object.py, honu_sort_keys and
-honu_key_objects in include/honu_codec.h).
+honu_key_objects in include/honu_codec.h). seek() and has() are the host
+statement of Cursor.Seek (iterator/cursor.go:44-55) and Collection.Has
+(collection.go:47-51) over such a sorted list; the batch form is
+Codec.seek_keys (honu_key_seek).
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional
+import bisect
+from typing import Iterable, List, Optional, Sequence
 
 from .metadata import Scalar
 
@@ -95,3 +99,34 @@ def sort(keys: Iterable[bytes]) -> List[bytes]:
     """sort.Sort(keys.Keys) (keys.go:126-130): ascending bytes.Compare, which
     is Python's order of bytes. Stable, which sort.Sort does not promise."""
     return sorted(bytes(k) for k in keys)
+
+
+def _prefix_successor(probe: bytes) -> Optional[bytes]:
+    """The least byte string above every string that has `probe` as prefix:
+    the probe without its trailing 0xff bytes, its last byte incremented.
+    None when there is none (an empty or all-0xff probe). Unlike ObjectLimit's
+    limit[16]++ (keys.go:88-91) this carries instead of wrapping."""
+    p = bytes(probe).rstrip(b"\xff")
+    return p[:-1] + bytes([p[-1] + 1]) if p else None
+
+
+def seek(sorted_keys: Sequence[bytes], probe: bytes):
+    """Cursor.Seek (iterator/cursor.go:44-55) over a sorted list of keys, and
+    where the probe's keys end: (pos, end). pos is the first position whose
+    key is >= probe by bytes.Compare, which is Python's order of bytes (a key
+    that has the probe as a proper prefix is greater), len(sorted_keys) where
+    Seek returns nil; end is the first position >= pos whose key does not have
+    the probe as prefix, so [pos, end) are the probe's keys. The batch form on
+    the GPU is Codec.seek_keys (honu_key_seek in include/honu_codec.h)."""
+    probe = bytes(probe)
+    pos = bisect.bisect_left(sorted_keys, probe)
+    nxt = _prefix_successor(probe)
+    end = len(sorted_keys) if nxt is None else bisect.bisect_left(sorted_keys, nxt, lo=pos)
+    return pos, end
+
+
+def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:
+    """Collection.Has (collection.go:47-51): key != nil && bytes.HasPrefix(key, probe)
+    of the key Seek lands on."""
+    pos, _ = seek(sorted_keys, probe)
+    return pos < len(sorted_keys) and bytes(sorted_keys[pos]).startswith(bytes(probe))

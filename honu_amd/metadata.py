@@ -57,6 +57,14 @@ INFO_DTYPE = np.dtype(
      "offsets": [0, 8, 16, 20, 24, 25], "itemsize": 32}
 )
 
+# honu_seek: one row of honu_key_seek per probe (Codec.seek_keys)
+SEEK_DTYPE = np.dtype(
+    {"names": ["pos", "end", "first", "latest", "flags"], "formats": ["<u4"] * 5,
+     "offsets": [0, 4, 8, 12, 16], "itemsize": 20}
+)
+SEEK_NONE = 0xFFFFFFFF
+SEEK_FOUND, SEEK_END, SEEK_EXACT, SEEK_FIRST_LIVE, SEEK_LATEST_LIVE, SEEK_SKIPPED = (1 << b for b in range(6))
+
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1
 HAS_PARENT = 1 << 2

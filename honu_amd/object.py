@@ -317,6 +317,24 @@ class Codec:
         return (obj_off[:8 * (n + 1)].view(torch.int64), latest[:4 * n].view(torch.int32),
                 objects[:8].view(torch.int64))
 
+    def seek_keys(self, sorted_keys, valid, probes, probe_len: int = 29, probe_status=None, order=None,
+                  info=None, m: Optional[int] = None):
+        """Cursor.Seek (iterator/cursor.go:44-55) of m probes (the first
+        probe_len bytes of each 29-byte row of `probes`) over sort_keys'
+        sorted column and valid count, which stay on the device: the
+        honu_seek rows (metadata.SEEK_DTYPE: pos, end, first, latest, flags)
+        as an int32 view of shape (m, 5), on the device. `order` (sort_keys')
+        enables first / latest, `info` (the decode's record info) the LIVE
+        flags; probes whose status is not OK are SKIPPED."""
+        n = sorted_keys.numel() // 29
+        if m is None:
+            m = probes.numel() // 29
+        out = self._empty(20 * m)
+        _lib.check(self.lib.honu_key_seek(
+            self.ctx, _lib.ptr(sorted_keys), _lib.ptr(valid), n, _lib.ptr(probes), _lib.ptr(probe_status),
+            probe_len, m, _lib.ptr(order), _lib.ptr(info), _lib.ptr(out), self.stream), "honu_key_seek")
+        return out[:20 * m].view(_torch().int32).view(m, 5)
+
 
 _default: Optional[Codec] = None
 

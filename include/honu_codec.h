@@ -18,6 +18,7 @@
  *   Object.Key()                object.go:57-64        honu_decode_keys (29-byte keys.Key column)
  *   sort.Sort(keys.Keys)        keys/keys.go:126-130   honu_sort_keys (stable order of the column)
  *   an object's versions        keys/keys.go:73-92     honu_key_objects (ranges of the order, latest)
+ *   Cursor.Seek, Has, Exists    iterator/cursor.go:44-55  honu_key_seek (positions of a batch of probes)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -333,6 +334,7 @@ uint64_t honu_sizeof_acl(void);
 uint64_t honu_sizeof_collection(void);
 uint64_t honu_sizeof_index(void);
 uint64_t honu_sizeof_record_info(void);
+uint64_t honu_sizeof_seek(void);
 const char *honu_status_string(int32_t status);
 /* Text of the last call-level failure on this thread (HIP error text etc.). */
 const char *honu_last_error(void);
@@ -570,6 +572,78 @@ int32_t honu_key_objects(honu_ctx *ctx, const uint8_t *d_keys, const uint32_t *d
                          const uint64_t *d_valid, uint64_t n, uint64_t *d_obj_off,
                          uint32_t *d_latest, uint64_t *d_objects,
                          void *d_work, uint64_t work_bytes, void *stream);
+
+/* One row of honu_key_seek per probe. */
+#define HONU_SEEK_NONE 0xFFFFFFFFu
+enum {
+    HONU_SEEK_FOUND       = 1u << 0, /* key != nil && bytes.HasPrefix(key, probe): Collection.Has, collection.go:49-50 */
+    HONU_SEEK_END         = 1u << 1, /* Seek returned nil: pos == valid (cursor_test.go:116-121) */
+    HONU_SEEK_EXACT       = 1u << 2, /* FOUND and probe_len == 29: the key itself is stored */
+    HONU_SEEK_FIRST_LIVE  = 1u << 3, /* FOUND and !info[first].tombstone: Collection.Exists AS WRITTEN (collection.go:57-64
+                                        reads the value at the Seek position, the object's LOWEST version) */
+    HONU_SEEK_LATEST_LIVE = 1u << 4, /* FOUND and !info[latest].tombstone: Exists / Retrieve AS DOCUMENTED
+                                        (collection.go:53-54, 97-101: the latest version) */
+    HONU_SEEK_SKIPPED     = 1u << 5  /* d_probe_status[q] != HONU_OK: not looked up */
+};
+typedef struct honu_seek {
+    uint32_t pos;    /* Cursor.Seek: first p in [0, valid) with bytes.Compare(sorted[p], probe) >= 0; valid when none */
+    uint32_t end;    /* first p >= pos whose key does not have the probe as prefix; [pos, end) are the probe's keys */
+    uint32_t first;  /* d_order[pos]     (record index), HONU_SEEK_NONE unless FOUND and d_order given */
+    uint32_t latest; /* d_order[end - 1] (record index), likewise */
+    uint32_t flags;
+} honu_seek;         /* 20 */
+
+/* Cursor.Seek (iterator/cursor.go:44-55; cursor_test.go:95-121: an existing
+ * key, a key between two keys, a key beyond the end) for a batch of m probes
+ * over a sorted key column: the step Collection.Has (collection.go:47-51),
+ * Collection.Exists (collection.go:55-65) and the lookups in the collections
+ * bucket (tx.go:123-125, store.go:287-288, 363-379) start from, and both ends
+ * of the range [ObjectPrefix, ObjectLimit) (keys/keys.go:73-92) that
+ * Retrieve and Versions (collection.go:97-110: "latest version of the
+ * object", "all versions, most recent first") range over.
+ * Inputs. d_sorted is the sorted column honu_sort_keys writes: 29 bytes per
+ * row, any byte alignment. Only rows [0, valid) are searched, valid =
+ * min(d_valid[0], n): the rows from valid on hold the bytes of invalid keys
+ * and are never returned, even where they equal a probe. d_valid is read on
+ * the device, so the call follows the sort on the same stream with no host
+ * round trip. Probe q is the first probe_len bytes (0..29, one length per
+ * call) of the 29-byte row at d_probes + 29*q, any byte alignment; all 29 m
+ * bytes must be readable, so a key column of honu_decode_keys is a probe
+ * column as it stands. probe_len 29 looks up a key, 17 an ObjectPrefix
+ * (keys.go:74-79), 16 a bare id as Has literally passes it; 0 matches every
+ * key.
+ * Results. The comparison is bytes.Compare: a key that has the probe as a
+ * proper prefix is greater than the probe. pos is therefore the lower bound
+ * over the probe_len-byte prefixes of the keys and end the upper bound; FOUND
+ * means pos < end. end stands for the second seek to ObjectLimit(), whose
+ * limit[16]++ wraps for an id that ends in 0xff (keys.go:88-91); the wrap is
+ * not reproduced, as in honu_key_objects. Equal keys form one run: pos its
+ * first position, end the position past its last.
+ * Optional inputs. d_probe_status (NULL: every probe takes part): a probe
+ * whose status is not HONU_OK gets {0, 0, NONE, NONE, SKIPPED}. d_order (the
+ * sort's) enables first and latest, which are its values at pos and end - 1.
+ * d_info (n rows; needs d_order) enables the two LIVE bits; an index of
+ * d_order that is not below n reads row n - 1 there, as in honu_key_objects.
+ * With valid == 0 every probe that takes part gets pos = end = 0 and END.
+ * With m == 0 nothing is launched or stored.
+ * The write set is exactly d_out[0, m). No workspace and no context scratch:
+ * calls on different streams may share a context. Asynchronous on `stream`,
+ * no host synchronisation, no allocation; replays from a captured graph.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for n or m above 2^32 - 1;
+ * HONU_E_ARG for a NULL ctx or d_valid, a NULL d_out or d_probes with m > 0,
+ * a NULL d_sorted with n > 0, probe_len > 29, d_info without d_order, or a
+ * misaligned pointer (4 bytes: d_out, d_order, d_probe_status; 8 bytes:
+ * d_valid, d_info).
+ * Param "seek_variant": 0 auto (the default), 1 the direct binary search over
+ * the column, 2 the fenced search, which resolves the top levels from "seek_fence"
+ * (get only) keys that each workgroup samples into LDS; auto takes the direct
+ * form for fewer than "seek_auto_probes" probes (1024) over more than
+ * "seek_auto_keys" rows (65536; both get only; n stands for the valid count,
+ * which the host does not know), and the fenced form otherwise. */
+int32_t honu_key_seek(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_valid, uint64_t n,
+                      const uint8_t *d_probes, const int32_t *d_probe_status, uint32_t probe_len,
+                      uint64_t m, const uint32_t *d_order, const honu_record_info *d_info,
+                      honu_seek *d_out, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
