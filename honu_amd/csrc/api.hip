@@ -94,13 +94,6 @@ static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)
 // record_variant 5 runs the batch entries through the split kernels of
 // variant 0, 6 through the fused decode at every size; variant 0 picks by size
 #define FUSED_DECODE_MIN_RECORDS (48ull << 10)
-// the A/B build (make ab: -DHONU_AB) adds the measurement-only copy variants and
-// the fused decode's measurement knobs
-#ifdef HONU_AB
-#define HONU_AB_BUILD 1
-#else
-#define HONU_AB_BUILD 0
-#endif
 
 // Fused kernels: persistent waves (2 workgroups of 4 waves per CU fit the LDS
 // and registers), fewer under a lane_blocks cap.
@@ -219,9 +212,7 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
     c->geom.per_record_blocks = env_int("HONU_RECORD_BLOCKS", prop.multiProcessorCount * 8);
     c->geom.lane_blocks = env_int("HONU_LANE_BLOCKS", 0);
     c->geom.copy_blocks = env_int("HONU_COPY_BLOCKS", prop.multiProcessorCount * 2);
-    c->geom.copy_variant = HONU_AB_BUILD ? env_int("HONU_COPY_VARIANT", 0) : 0;
     c->geom.record_variant = env_int("HONU_RECORD_VARIANT", 0);
-    c->geom.encode_variant = HONU_AB_BUILD && env_int("HONU_ENCODE_VARIANT", 0) == 1 ? 1 : 0;  // 0 default
     if (c->geom.record_variant != 5 && c->geom.record_variant != 6)
         c->geom.record_variant = 0;
     c->acl_inplace = env_int("HONU_ACL_INPLACE", 1) != 0;
@@ -233,8 +224,6 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
     c->guard_blocks = env_int("HONU_GUARD_BLOCKS", 0);
     if (c->guard_blocks < 0) c->guard_blocks = 0;
     const uint64_t n = c->max_n;
-    const uint64_t np = 0;
-    const uint64_t map_cap = HONU_AB_BUILD ? 1ull << 22 : 0;  // tile map (A/B sweep copy)
     const uint64_t tiles = (n + HONU_WAVE - 1) / HONU_WAVE;
     const uint64_t scan_words = scan_status_words(n);
     // 3 status words per tile, then 3 per 64-tile group (lookback.h
@@ -244,8 +233,8 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
     // (+ the copies' range-tail counters: a ring of 128-byte lines)
     const uint64_t lb_bytes =
         2 * sizeof(LbState) + 8 * (lb_dec_words + scan_words) + COPY_TICKET_LINES * 4 * COPY_TICKET_STRIDE;
-    const uint64_t bytes = 8 * (3 * n + 3 * n + 4 + np) + sizeof(DecodeScratch) * n + 32 * n +
-                           sizeof(EncAclPos) * n + 4 * map_cap + lb_bytes + 256;
+    const uint64_t bytes = 8 * (3 * n + 3 * n + 4) + sizeof(DecodeScratch) * n + 32 * n +
+                           sizeof(EncAclPos) * n + lb_bytes + 256;
     if (hipMalloc(&c->ws, bytes) != hipSuccess) {
         c->ws = nullptr;
         char msg[96];
@@ -284,9 +273,7 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
     c->scratch = (DecodeScratch *)w;
     c->reg_inline = (uint32_t *)(c->scratch + n);
     c->enc_acl = (EncAclPos *)(c->reg_inline + 8 * n);
-    c->geom.tile_map = (uint32_t *)(c->enc_acl + n);
-    c->geom.tile_map_cap = map_cap;
-    c->lb_dec = (LbState *)(c->geom.tile_map + map_cap);
+    c->lb_dec = (LbState *)(c->enc_acl + n);
     c->scan.lb = c->lb_dec + 1;
     c->lb_dec_status = (uint64_t *)(c->scan.lb + 1);
     c->lb_dec_words = lb_dec_words;
@@ -346,10 +333,10 @@ int32_t honu_ctx_set_param(honu_ctx *ctx, const char *name, int64_t value) {
         ctx->spec_off = (uint32_t)value;
     }
     else if (!strcmp(name, "copy_steal") && (value == 0 || value == 1)) ctx->geom.copy_steal = (int)value;
-    else if (!strcmp(name, "copy_variant") && value >= 0 && (value == 0 || HONU_AB_BUILD))
-        ctx->geom.copy_variant = (int)value;
-    else if (!strcmp(name, "encode_variant") && (value == 0 || (value == 1 && HONU_AB_BUILD)))
-        ctx->geom.encode_variant = (int)value;
+    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant")) {
+        // kept for compatibility: there is one copy engine and one header/tail encoder, form 0
+        if (value != 0) return arg_fail(name);
+    }
     else if (!strcmp(name, "record_variant") &&
              (value == 0 || value == 5 || value == 6))
         ctx->geom.record_variant = (int)value;
@@ -374,8 +361,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "speculate_backoff"))  // calls the next call starts without speculation
         *value = __atomic_load_n(ctx->spec_seen, __ATOMIC_RELAXED) ? SPEC_BACKOFF_CALLS : ctx->spec_off;
     else if (!strcmp(name, "copy_steal")) *value = ctx->geom.copy_steal;
-    else if (!strcmp(name, "copy_variant")) *value = ctx->geom.copy_variant;
-    else if (!strcmp(name, "encode_variant")) *value = ctx->geom.encode_variant;
+    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant")) *value = 0;  // (see set_param)
     else if (!strcmp(name, "record_variant")) *value = ctx->geom.record_variant;
     else if (!strcmp(name, "walk_flag_checks")) *value = decode_walk_flag_checks();  // read only: the build's
     else if (!strcmp(name, "sort_tile")) *value = sort_tile();  // read only: keys per workgroup per sort pass
@@ -429,17 +415,11 @@ static int32_t encode_records(honu_ctx *ctx, const honu_meta *d_meta, const uint
     HIPCHK(hipSetDevice(ctx->device));
     if (n > ctx->max_n) return HONU_E_WORKSPACE;
     ctx->enc_form = units ? 2 : 1;  // (the payload call checks it: never mix the two forms)
-#ifdef HONU_AB
-    if (ctx->geom.encode_variant == 1 && !units) {  // one launch, 16 lanes per record (enc.hip, A/B build only)
-        HIPCHK(launch_encode_tail_grp(d_meta, d_var, d_acl, d_regions, d_payload_off, n, d_out,
-                                      out_cap, d_out_off, d_status, ctx->geom.lane_blocks,
-                                      (hipStream_t)stream));
-        return HONU_OK;
-    }
-#endif
-    // encode_variant 0 (default, measured faster: DESIGN §3): header + tail
-    // with the ACL lists' partial end chunks (one record per lane), then the
-    // lists' whole chunks (16 lanes per record)
+    // header + tail with the ACL lists' partial end chunks (one record per
+    // lane), then the lists' whole chunks (16 lanes per record). (Measured and
+    // not kept, source in commit 426ce70 enc.hip: the whole record by a
+    // 16-lane group in one launch, DESIGN_HISTORY "Round 3: a header/tail
+    // encoder without a serial writer".)
     hipStream_t s = (hipStream_t)stream;
     // (auto: not on a CU-masked or prioritised caller stream, whose placement
     // the fork would escape)

@@ -129,6 +129,9 @@ HONU_HD uint32_t uvarint_len(uint64_t x) {
     uint32_t bits = 64u - (uint32_t)__builtin_clzll(x | 1ull);
     return (bits + 6u) / 7u;
 }
+// Length of a length-prefixed lani field: PutUvarint(len), then the bytes.
+HONU_HD uint64_t frame_len(uint64_t len) { return uvarint_len(len) + len; }
+#define GO_MAX_ALLOC (1ull << 48)  // runtime maxAlloc, linux/amd64
 // binary.PutVarint zig-zag (encoding/binary/varint.go PutVarint).
 HONU_HD uint64_t zigzag(int64_t x) {
     uint64_t ux = (uint64_t)x << 1;
@@ -194,15 +197,6 @@ HONU_DEV u32x4 funnel16(u32x4 lo, u32x4 hi, uint32_t p) {
     return r;
 }
 
-template <bool NT> HONU_DEV u32x4 ld16(const u32x4 *p) {
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <bool NT> HONU_DEV void st16(u32x4 *p, u32x4 v) {
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
 // Byte copy by the lanes of one wave (edges and small spans).
 HONU_DEV void wave_copy_bytes(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src,
                               uint64_t n) {
@@ -215,16 +209,12 @@ HONU_DEV void wave_copy_bytes(uint8_t *__restrict__ dst, const uint8_t *__restri
 // never touched. Source chunks are read with aligned 16-byte loads: an
 // aligned 16-byte block holding at least one source byte never crosses a
 // page, so the over-read is always mapped.
-// NT: non-temporal cache policy, 0 none, 1 loads and stores, 2 loads only,
-// 3 stores only; 4: a misaligned source is read with one unaligned 16-byte
-// load per chunk instead of two aligned loads and a funnel.
 // The head bytes, the tail bytes and the first UNROLL x 64 chunks are all
 // loaded before any of them is stored, so a short segment (the common case
 // for Small records: 2.5 KB) costs one round trip, not three.
-template <int UNROLL = 4, int NT = 0>
+template <int UNROLL = 4>
 HONU_DEV void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint64_t n) {
     if (n == 0) return;
-    constexpr bool NTL = NT == 1 || NT == 2, NTS = NT == 1 || NT == 3;
     const uint32_t lane = lane_id();
     uint64_t head = (16u - ((uint64_t)dst & 15u)) & 15u;
     if (head > n) head = n;
@@ -236,15 +226,11 @@ HONU_DEV void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ s
     const uint32_t p = (uint32_t)((uint64_t)bsrc & 15u);  // wave-uniform
     const u32x4 *__restrict__ s4 = reinterpret_cast<const u32x4 *>(bsrc - p);
     auto load = [&](uint64_t c, u32x4 &a, u32x4 &b) {
-        if (NT == 4 && p) {
-            a = *reinterpret_cast<const u32x4u *>(bsrc + 16 * c);
-        } else {
-            a = ld16<NTL>(&s4[c]);
-            if (p) b = ld16<NTL>(&s4[c + 1]);
-        }
+        a = s4[c];
+        if (p) b = s4[c + 1];
     };
     auto store = [&](uint64_t c, const u32x4 &a, const u32x4 &b) {
-        st16<NTS>(&d4[c], (p == 0 || NT == 4) ? a : funnel16(a, b, p));
+        d4[c] = p == 0 ? a : funnel16(a, b, p);
     };
     // round 0: edges and the first chunks
     uint8_t hv = 0, tv = 0;

@@ -30,10 +30,6 @@ struct EncodeSegments {
 
     HONU_DEV uint64_t start(uint64_t i) const { return payload_off[i]; }
     HONU_DEV uint64_t lo() const { return payload_off[0]; }
-    HONU_DEV uint64_t end(uint64_t i, uint64_t total_abs) const {
-        (void)total_abs;
-        return payload_off[i + 1];
-    }
     bool units;  // honu_encode_payloads_units: the encoder wrote the payload's partial end 64-byte units
     HONU_DEV bool get(uint64_t i, uint64_t &len, const uint8_t *&src, uint8_t *&dst, uint64_t &skip) const {
         // the header/tail encoder may still be running on another stream:
@@ -72,8 +68,7 @@ struct DecodeSegments {
 
     HONU_DEV uint64_t start(uint64_t i) const { return offs[3 * i + 2]; }
     HONU_DEV uint64_t lo() const { return 0; }
-    HONU_DEV uint64_t end(uint64_t i, uint64_t total_abs) const { return i + 1 < n_ ? offs[3 * i + 5] : total_abs; }
-    uint64_t n_;
+    uint64_t n_;  // (read by the retired sweep form only; stays until the kernel's arguments may move)
     HONU_DEV bool get(uint64_t i, uint64_t &len, const uint8_t *&src, uint8_t *&dst, uint64_t &skip) const {
         skip = 0;
         const int32_t st = info[i].data_status;  // every field in one round trip
@@ -95,7 +90,6 @@ struct SpanSegments {
 
     HONU_DEV uint64_t start(uint64_t i) const { return offs[i]; }
     HONU_DEV uint64_t lo() const { return 0; }
-    HONU_DEV uint64_t end(uint64_t i, uint64_t total_abs) const { (void)total_abs; return offs[i + 1]; }
     HONU_DEV bool get(uint64_t i, uint64_t &len, const uint8_t *&src, uint8_t *&dst, uint64_t &skip) const {
         skip = 0;
         const int32_t st = info[i].data_status;  // every field in one round trip
@@ -112,20 +106,20 @@ struct SpanSegments {
 #ifndef COPY_FEW_WAVES_MIN
 #define COPY_FEW_WAVES_MIN (64u << 10)
 #endif
+constexpr int COPY_UNROLL = 4;  // 16-byte chunks in flight per lane
 
-// TWO (the default; variant 40 of the A/B build without it): a launch of long
-// segments on average (>= COPY_FEW_WAVES_MIN) gives its first 1 /
-// SMALL_SEG_WAVES_FACTOR of waves the long segments (byte ranges as below,
-// short segments skipped) and the other waves, which used to return at once,
-// the short ones (each wave a range of segment indices, short segments
-// whole): the short records of a mixed batch no longer hold up the few
-// streaming waves. 1M Mixed encode + decode 1238-1248 -> 1266-1268 GiB/s on
-// one box, 1152-1176 -> 1189-1230 on another (interleaved; every Large and
-// XLarge payload is >= 64 KB, so those batches have no short class, and they
-// measured equal within the runs' order effect; profiles/r05/copy_classes/).
-// (Every wave on every segment instead: Mixed 7 % slower, the long segments'
-// streams too many.)
-template <class Seg, int UNROLL>
+// Two segment classes: a launch of long segments on average (>=
+// COPY_FEW_WAVES_MIN) gives its first 1 / SMALL_SEG_WAVES_FACTOR of waves the
+// long segments (byte ranges as below, short segments skipped) and the other
+// waves, which used to return at once, the short ones (each wave a range of
+// segment indices, short segments whole): the short records of a mixed batch
+// no longer hold up the few streaming waves. 1M Mixed encode + decode
+// 1238-1248 -> 1266-1268 GiB/s on one box, 1152-1176 -> 1189-1230 on another
+// (interleaved; every Large and XLarge payload is >= 64 KB, so those batches
+// have no short class, and they measured equal within the runs' order effect;
+// profiles/r05/copy_classes/). (Every wave on every segment instead: Mixed 7 %
+// slower, the long segments' streams too many.)
+template <class Seg>
 HONU_DEV void copy_short_run(const Seg &seg, uint64_t i0, uint64_t i1, uint64_t short_max) {
     uint64_t len_nx = 0, skip = 0;
     const uint8_t *src_nx = nullptr;
@@ -137,42 +131,14 @@ HONU_DEV void copy_short_run(const Seg &seg, uint64_t i0, uint64_t i1, uint64_t 
         uint8_t *dst = dst_nx;
         const bool ok = ok_nx;
         if (i + 1 < i1) ok_nx = seg.get(i + 1, len_nx, src_nx, dst_nx, skip);
-        if (ok && len < short_max) wave_copy<UNROLL, 0>(dst, src, len);
-    }
-}
-
-// tickets (A/B build, variant 46): the index runs' last eighths from a
-// counter pair, as the long class's range tails (below)
-template <class Seg, int UNROLL, bool TAILS = false>
-HONU_DEV void copy_short_class(const Seg &seg, uint64_t n, uint64_t v, uint64_t V, uint64_t short_max,
-                               uint32_t *tickets = nullptr) {
-    if constexpr (!TAILS) {
-        copy_short_run<Seg, UNROLL>(seg, n * v / V, n * (v + 1) / V, short_max);
-        (void)tickets;
-        return;
-    }
-    auto cut = [&](uint64_t u) {  // where run u's tail starts
-        const uint64_t a = n * u / V, b = n * (u + 1) / V;
-        return b - (((b - a) * 8) >> 6);
-    };
-    copy_short_run<Seg, UNROLL>(seg, n * v / V, cut(v), short_max);
-    for (;;) {
-        uint32_t t = 0;
-        if (__lane_id() == 0) t = atomicAdd(&tickets[0], 1u);
-        t = __shfl(t, 0);
-        if (t >= V) break;
-        copy_short_run<Seg, UNROLL>(seg, cut(t), n * (t + 1) / V, short_max);
-    }
-    if (__lane_id() == 0 && atomicAdd(&tickets[1], 1u) == (uint32_t)V - 1) {
-        atomicExch(&tickets[0], 0u);
-        atomicExch(&tickets[1], 0u);
+        if (ok && len < short_max) wave_copy<COPY_UNROLL>(dst, src, len);
     }
 }
 
 // The logical range [lo, hi) of a streaming wave: its first segment by binary
 // search, then forward across segment boundaries (skip_short: segments under
 // short_max are the short class's).
-template <class Seg, int UNROLL, int NT>
+template <class Seg>
 HONU_DEV void copy_range(const Seg &seg, uint64_t n, uint64_t lo, uint64_t hi, bool skip_short,
                          uint64_t short_max) {
     if (lo >= hi) return;
@@ -209,7 +175,7 @@ HONU_DEV void copy_range(const Seg &seg, uint64_t n, uint64_t lo, uint64_t hi, b
         const uint64_t e = s + len;
         const uint64_t y = e < hi ? e : hi;
         if (x < y)
-            wave_copy<UNROLL, NT>(dst + (x - s), src + (x - s), y - x);
+            wave_copy<COPY_UNROLL>(dst + (x - s), src + (x - s), y - x);
     }
 }
 
@@ -230,13 +196,11 @@ HONU_DEV void copy_range(const Seg &seg, uint64_t n, uint64_t lo, uint64_t hi, b
 // equal; with it on 1M Small too, +1.9 % (2.6 KB payloads: hence the bound).
 #define COPY_STEAL_MIN (16u << 10)
 #define COPY_STEAL 8u
-template <class Seg, int UNROLL, int NT, bool TWO = false, bool STAILS = false>
+template <class Seg>
 __global__ __launch_bounds__(HONU_BLOCK) void k_copy_segments(Seg seg, uint64_t n,
                                                                const uint64_t *__restrict__ total_p,
-                                                               uint64_t short_max = COPY_FEW_WAVES_MIN,
-                                                               uint32_t *tickets = nullptr,
-                                                               uint32_t steal = COPY_STEAL,
-                                                               uint32_t *short_tickets = nullptr) {
+                                                               uint64_t short_max, uint32_t *tickets,
+                                                               uint32_t steal) {
     uint64_t W = (uint64_t)gridDim.x * HONU_WAVES_PER_BLOCK;
     const uint64_t w = (uint64_t)blockIdx.x * HONU_WAVES_PER_BLOCK + wave_in_block();
     const uint64_t base = seg.lo();
@@ -248,11 +212,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_copy_segments(Seg seg, uint64_t 
     if (few) {
         const uint64_t Wall = W;
         W /= SMALL_SEG_WAVES_FACTOR;
-        if constexpr (TWO) {
-            if (w >= W) {
-                copy_short_class<Seg, UNROLL, STAILS>(seg, n, w - W, Wall - W, short_max, short_tickets);
-                return;
-            }
+        if (w >= W) {  // the short class: run w - W of Wall - W index runs
+            const uint64_t v = w - W, V = Wall - W;
+            copy_short_run(seg, n * v / V, n * (v + 1) / V, short_max);
+            return;
         }
     }
     if (w >= W) return;
@@ -266,7 +229,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_copy_segments(Seg seg, uint64_t 
         auto cut = [&](uint64_t l, uint64_t h) {  // where a range's tail starts (steal / 64 of it)
             return h - ((((h - l) * steal) >> 6) & ~15ull);
         };
-        copy_range<Seg, UNROLL, NT>(seg, n, lo, cut(lo, hi), TWO && few, short_max);
+        copy_range(seg, n, lo, cut(lo, hi), few, short_max);
         for (;;) {
             uint32_t t = 0;
             if (__lane_id() == 0) t = atomicAdd(&tickets[0], 1u);
@@ -274,7 +237,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_copy_segments(Seg seg, uint64_t 
             if (t >= W) break;  // each wave's last take: W of them past the tails
             uint64_t l, h;
             range(t, l, h);
-            copy_range<Seg, UNROLL, NT>(seg, n, cut(l, h), h, TWO && few, short_max);
+            copy_range(seg, n, cut(l, h), h, few, short_max);
         }
         if (__lane_id() == 0 && atomicAdd(&tickets[1], 1u) == (uint32_t)W - 1) {
             atomicExch(&tickets[0], 0u);  // every wave has taken its last ticket
@@ -282,133 +245,35 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_copy_segments(Seg seg, uint64_t 
         }
         return;
     }
-    copy_range<Seg, UNROLL, NT>(seg, n, lo, hi, TWO && few, short_max);
+    copy_range(seg, n, lo, hi, few, short_max);
 }
 
-#ifdef HONU_AB
-// ------------------------------------------------------------------------
-// Sweep form: the logical space is cut into tiles of T bytes and wave w
-// copies tiles w, w+W, w+2W, ... so that at any moment all waves work inside
-// one window of W*T bytes (DRAM rows opened by one wave are hit by its
-// neighbours) instead of W scattered streams. A prep kernel maps every tile to
-// the first segment overlapping it. T grows with the batch so the map fits
-// its fixed capacity.
-// ------------------------------------------------------------------------
-#define SWEEP_TILE_MIN (16u << 10)
-
-HONU_DEV uint64_t sweep_tile(uint64_t total, uint64_t map_cap) {
-    uint64_t t = (total + map_cap - 1) / map_cap;
-    t = (t + 4095) & ~4095ull;
-    return t < SWEEP_TILE_MIN ? SWEEP_TILE_MIN : t;
-}
-
-template <class Seg>
-__global__ __launch_bounds__(HONU_BLOCK) void k_tile_map(Seg seg, uint64_t n,
-                                                         const uint64_t *__restrict__ total_p,
-                                                         uint32_t *__restrict__ map, uint64_t map_cap) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t base = seg.lo();
-    const uint64_t total = *total_p - base;
-    const uint64_t T = sweep_tile(total, map_cap);
-    const uint64_t s = seg.start(i) - base, e = seg.end(i, *total_p) - base;
-    for (uint64_t t = (s + T - 1) / T; t * T < e; t++) map[t] = (uint32_t)i;
-}
-
-template <class Seg, int UNROLL>
-__global__ __launch_bounds__(HONU_BLOCK) void k_copy_sweep(Seg seg, uint64_t n,
-                                                            const uint64_t *__restrict__ total_p,
-                                                            const uint32_t *__restrict__ map,
-                                                            uint64_t map_cap) {
-    const uint64_t W = (uint64_t)gridDim.x * HONU_WAVES_PER_BLOCK;
-    const uint64_t w = (uint64_t)blockIdx.x * HONU_WAVES_PER_BLOCK + wave_in_block();
-    const uint64_t base = seg.lo();
-    const uint64_t total = *total_p - base;
-    const uint64_t T = sweep_tile(total, map_cap);
-    const uint64_t ntiles = (total + T - 1) / T;
-    for (uint64_t t = w; t < ntiles; t += W) {
-        const uint64_t lo = base + t * T;
-        const uint64_t hi = lo + T < base + total ? lo + T : base + total;
-        for (uint64_t i = map[t]; i < n; i++) {
-            uint64_t s = seg.start(i);
-            if (s >= hi) break;
-            uint64_t len;
-            const uint8_t *src;
-            uint8_t *dst;
-            uint64_t skip;
-            if (!seg.get(i, len, src, dst, skip)) continue;
-            s += skip;
-            const uint64_t x = s > lo ? s : lo;
-            const uint64_t e = s + len;
-            const uint64_t y = e < hi ? e : hi;
-            if (x < y) wave_copy<UNROLL, 0>(dst + (x - s), src + (x - s), y - x);
-        }
-    }
-}
-
-#endif  // HONU_AB
-
-// Copy-engine variants (A/B build only, tools/tune_copy.py): 1-5 contiguous
-// per-wave ranges {unroll, non-temporal}; 6-7 the sweep form; 11 / 12
-// non-temporal loads only / stores only; 13-15 one unaligned 16-byte load per
-// chunk instead of two aligned loads and a funnel; 40 without the short-
-// segment class; 44 without the range tails (every variant but 0 and 45 runs
-// without them); 45 the tails' share from HONU_COPY_STEAL; 46 the range tails
-// and the short class's run tails. The product library has variant 0 only (unroll 4, default
-// cache policy, two segment classes: measured fastest).
+// One form: unroll 4, default cache policy, two segment classes, range tails
+// (context param "copy_steal"). Measured and not kept (sources in git history,
+// commit 426ce70, there as copy variants of the A/B build; numbers in
+// DESIGN_HISTORY.md, "two segment classes" / "range tails from a counter" and
+// the paragraphs after them unless another place is named):
+// non-temporal loads and stores, both / loads only / stores only (variants
+// 2-3, 11, 12): 1M Large 1270 / 1197-1230 / 1223 against 1345 GiB/s in round
+// 1, 1166-1210 against 1252-1332 in round 5 (profiles/r05/copy_nt/); the sweep
+// form, a tile -> segment map and waves striding tiles inside one window
+// (6-7): not better (round 1, "a tile-interleaved sweep variant"); one
+// unaligned 16-byte load per chunk instead of two aligned loads and a funnel
+// (13-15): Large encode copy 5.18 -> 4.85 TB/s, decode 5.89 -> 5.50; unroll
+// 8 / 2 / 16 (1, 4, 5): 8 is -2.4 % on Medium and slower on Small, 2 is
+// -0.6 % on Small, and the size class is known on the device only
+// (profiles/r05/copy_unroll/); one segment class (40): the numbers above
+// copy_short_run; the short class's bound from the environment (42): 32 KB
+// within the noise, 128 and 256 KB slower on Mixed; the tails' share from the
+// environment (45): 4 / 16 / 24 of 64 slower than 8 (share_sweep/); run tails
+// for the short class from a second counter pair (46): Mixed encode 30.64
+// against 30.26 ms, within the run-order effect (short_tails/).
 template <class Seg>
 static hipError_t launch_copy(const LaunchGeom &g, const Seg &seg, uint64_t n,
                               const uint64_t *total, uint32_t *tickets, hipStream_t s) {
     const dim3 grid(g.copy_blocks * SMALL_SEG_WAVES_FACTOR), block(HONU_BLOCK);
-#ifdef HONU_AB
-    if (g.copy_variant >= 6 && g.copy_variant <= 7) {
-        if (!g.tile_map) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_tile_map<Seg>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                           seg, n, total, g.tile_map, g.tile_map_cap);
-        if (g.copy_variant == 7)
-            hipLaunchKernelGGL((k_copy_sweep<Seg, 8>), grid, block, 0, s, seg, n, total, g.tile_map, g.tile_map_cap);
-        else
-            hipLaunchKernelGGL((k_copy_sweep<Seg, 4>), grid, block, 0, s, seg, n, total, g.tile_map, g.tile_map_cap);
-        return hipGetLastError();
-    }
-    switch (g.copy_variant) {
-    case 1: hipLaunchKernelGGL((k_copy_segments<Seg, 8, 0>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 2: hipLaunchKernelGGL((k_copy_segments<Seg, 4, 1>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 3: hipLaunchKernelGGL((k_copy_segments<Seg, 8, 1>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 4: hipLaunchKernelGGL((k_copy_segments<Seg, 2, 0>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 5: hipLaunchKernelGGL((k_copy_segments<Seg, 16, 0>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 11: hipLaunchKernelGGL((k_copy_segments<Seg, 4, 2>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 12: hipLaunchKernelGGL((k_copy_segments<Seg, 4, 3>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 13: hipLaunchKernelGGL((k_copy_segments<Seg, 4, 4>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 14: hipLaunchKernelGGL((k_copy_segments<Seg, 8, 4>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 15: hipLaunchKernelGGL((k_copy_segments<Seg, 2, 4>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 40: hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, false>), grid, block, 0, s, seg, n, total); return hipGetLastError();
-    case 45: {  // the range tails' share (/ 64) from the environment (HONU_COPY_STEAL)
-        static const uint32_t st = getenv("HONU_COPY_STEAL") ? (uint32_t)atoi(getenv("HONU_COPY_STEAL")) : COPY_STEAL;
-        if (st > 64) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, true>), grid, block, 0, s, seg, n, total,
-                           (uint64_t)COPY_FEW_WAVES_MIN, tickets, st);
-        return hipGetLastError();
-    }
-    case 46:  // + the short class's run tails (tickets[2..3] of the kind's line)
-        hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, true, true>), grid, block, 0, s, seg, n, total,
-                           (uint64_t)COPY_FEW_WAVES_MIN, tickets, COPY_STEAL, tickets + 2);
-        return hipGetLastError();
-    case 44:  // range tails off
-        hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, true>), grid, block, 0, s, seg, n, total,
-                           (uint64_t)COPY_FEW_WAVES_MIN, nullptr);
-        return hipGetLastError();
-    case 42: {  // the short class's bound from the environment (bytes)
-        static const uint64_t sm = getenv("HONU_COPY_SHORT_MAX") ? strtoull(getenv("HONU_COPY_SHORT_MAX"), nullptr, 10)
-                                                                 : (uint64_t)COPY_FEW_WAVES_MIN;
-        hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, true>), grid, block, 0, s, seg, n, total, sm);
-        return hipGetLastError();
-    }
-    default: break;
-    }
-#endif
-    hipLaunchKernelGGL((k_copy_segments<Seg, 4, 0, true>), grid, block, 0, s, seg, n, total,
-                       (uint64_t)COPY_FEW_WAVES_MIN, g.copy_steal ? tickets : nullptr);
+    hipLaunchKernelGGL((k_copy_segments<Seg>), grid, block, 0, s, seg, n, total,
+                       (uint64_t)COPY_FEW_WAVES_MIN, g.copy_steal ? tickets : nullptr, COPY_STEAL);
     return hipGetLastError();
 }
 
@@ -435,7 +300,7 @@ hipError_t launch_decode_copy(const LaunchGeom &g, const uint8_t *rec, uint64_t 
                               const uint64_t *offs, const uint64_t *totals, uint8_t *data,
                               hipStream_t s) {
     if (n == 0) return hipSuccess;
-    DecodeSegments seg{rec, info, scratch, offs, data, n};
+    DecodeSegments seg{rec, info, scratch, offs, data, n};  // (n: the unread n_)
     return launch_copy(g, seg, n, totals + 2, g.copy_tickets, s);
 }
 

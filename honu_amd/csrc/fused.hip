@@ -659,8 +659,8 @@ __global__ __launch_bounds__(HONU_BLOCK, 2) void k_decode_fused(HONU_FUSED_PARAM
 }
 
 // The guarded launch (MODE 2, ticket tiles) in one-wave workgroups of 19 KB
-// LDS (the four-wave ones take 78 KB). Where a no-op guard still waits is
-// registers, not LDS: beside the other slot's tail encoder (k_encode_meta_lane,
+// LDS (round 4's four-wave ones, commit 426ce70, took 78 KB). A no-op guard
+// still waits for registers, not LDS: beside the other slot's tail encoder (k_encode_meta_lane,
 // 180 VGPRs at 2 waves per SIMD: 144 of a SIMD's 512 free) no decode wave fits
 // (227-255 VGPRs; capped by amdgpu_num_vgpr the walk still needs 169 with 105
 // spilled), so it waits 25-60 us for an encoder wave to end in every Small
@@ -741,13 +741,6 @@ hipError_t launch_decode_fused(const uint8_t *rec, const uint64_t *rec_off, uint
         uint64_t gw = b * HONU_WAVES_PER_BLOCK;
         if (guard_blocks > 0 && (uint64_t)guard_blocks < gw) gw = (uint64_t)guard_blocks;
         const dim3 g2((unsigned)gw), b2(HONU_WAVE);
-#ifdef HONU_AB  // (A/B build: HONU_GUARD_WIDE=1, the round-4 guard of four-wave workgroups)
-        static const bool wide = getenv("HONU_GUARD_WIDE") && atoi(getenv("HONU_GUARD_WIDE")) == 1;
-        if (wide) {
-            HONU_FUSED_LAUNCH(2);
-            return hipGetLastError();
-        }
-#endif
         if (inplace)
             hipLaunchKernelGGL((k_decode_guard<true>), g2, b2, 0, s, rec, rec_off, n, O, lb, lb_status,
                                lb_gstatus, lb_words, spec_seen, recoveries, false);

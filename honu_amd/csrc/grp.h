@@ -7,8 +7,6 @@
 
 namespace honu {
 
-#define GO_MAX_ALLOC (1ull << 48)  // runtime maxAlloc, linux/amd64
-
 constexpr int GRP = 16;                       // lanes per record
 #ifndef FILL_G
 #define FILL_G 16                             // decode fill: lanes per record

@@ -22,7 +22,6 @@ namespace honu {
 HONU_DEV bool gspan_in(uint64_t off, uint64_t len, uint64_t var_len) {
     return len == 0 || (off <= var_len && len <= var_len - off);
 }
-HONU_DEV uint64_t gframe_len(uint64_t len) { return uvarint_len(len) + len; }
 
 template <int G>
 HONU_DEV void k_encode_sizes_grp_one(uint64_t i, uint8_t *smem, const honu_meta *__restrict__ meta, uint64_t var_len, const honu_acl *__restrict__ acl,
@@ -70,9 +69,9 @@ HONU_DEV void k_encode_sizes_grp_one(uint64_t i, uint8_t *smem, const honu_meta 
                      1 + uvarint_len(zigzag(m.version_created));
             t += 1;  // Schema flag
             if (pr & HONU_HAS_SCHEMA)
-                t += gframe_len(m.schema_name.len) + uvarint_len(m.schema_major) +
+                t += frame_len(m.schema_name.len) + uvarint_len(m.schema_major) +
                      uvarint_len(m.schema_minor) + uvarint_len(m.schema_patch);
-            t += gframe_len(m.mime.len) + 33;  // MIME, Owner, Group, Permissions
+            t += frame_len(m.mime.len) + 33;  // MIME, Owner, Group, Permissions
             t += uvarint_len(na) + uvarint_len(nr);
             uint64_t part = 0;  // this lane's share of the lists
             if (sized) t += m.acl_bytes;  // no ACL entry read
@@ -80,10 +79,10 @@ HONU_DEV void k_encode_sizes_grp_one(uint64_t i, uint8_t *smem, const honu_meta 
                 for (uint64_t k = r; k < na; k += G) part += acl[ao + k].present ? 18 : 1;
             for (uint64_t k = r; k < nr; k += G) part += uvarint_len(reg[ro + k]);
             t += 3;  // Publisher, Encryption, Compression flags
-            if (pr & HONU_HAS_PUBLISHER) t += 32 + gframe_len(m.ip_address.len) + gframe_len(m.user_agent.len);
+            if (pr & HONU_HAS_PUBLISHER) t += 32 + frame_len(m.ip_address.len) + frame_len(m.user_agent.len);
             if (pr & HONU_HAS_ENCRYPTION)
-                t += gframe_len(m.public_key_id.len) + gframe_len(m.encryption_key.len) +
-                     gframe_len(m.hmac_secret.len) + gframe_len(m.signature.len) + 3;
+                t += frame_len(m.public_key_id.len) + frame_len(m.encryption_key.len) +
+                     frame_len(m.hmac_secret.len) + frame_len(m.signature.len) + 3;
             if (pr & HONU_HAS_COMPRESSION) t += 1 + uvarint_len(zigzag(m.compression_level));
             t += 1 + uvarint_len(zigzag(m.created)) + uvarint_len(zigzag(m.modified));
             t += grp_sum64<G>(part);
@@ -276,9 +275,9 @@ HONU_DEV void k_encode_acl_grp_one(uint64_t i, const honu_meta *__restrict__ met
                  uvarint_len(zigzag(m.version_created));
         t += 1;  // Schema flag
         if (pr & HONU_HAS_SCHEMA)
-            t += gframe_len(m.schema_name.len) + uvarint_len(m.schema_major) + uvarint_len(m.schema_minor) +
+            t += frame_len(m.schema_name.len) + uvarint_len(m.schema_major) + uvarint_len(m.schema_minor) +
                  uvarint_len(m.schema_patch);
-        t += gframe_len(m.mime.len) + 33 + uvarint_len(na);  // MIME, Owner, Group, Permissions, count
+        t += frame_len(m.mime.len) + 33 + uvarint_len(na);  // MIME, Owner, Group, Permissions, count
         const uint64_t dlen = payload_off[i + 1] - payload_off[i];
         uint64_t miss = 0;  // nil entries
         for (uint64_t k = r; k < na; k += G) miss += acl[ao + k].present ? 0 : 1;

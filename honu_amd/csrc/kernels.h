@@ -97,9 +97,6 @@ struct LaunchGeom {
     int lane_blocks;        // cap on blocks for the lane / group / window kernels
                             // (0: one block per 256 lanes of work, no cap)
     int copy_blocks;        // blocks of the byte-balanced copy kernel
-    int copy_variant;       // copy engine variant (copy.hip: unroll depth / cache policy)
-    int encode_variant;     // header/tail encoder: 0 lane writer + ACL group kernel (lane.hip,
-                            // grp.hip; default), 1 group layout (enc.hip, A/B build only)
     int record_variant;     // per-record kernels: 0 auto (the fastest measured form
                             // of each; honu_decode_batch single-launch from 48 K
                             // records), 5 split decode, 6 single-launch decode
@@ -107,8 +104,6 @@ struct LaunchGeom {
                             // per-group / per-lane forms 1-4: DESIGN §3)
     int seek_variant;       // honu_key_seek: 0 auto (by the probe and row counts), 1 the direct
                             // binary search, 2 the fenced one (seek.hip)
-    uint32_t *tile_map;     // sweep-form tile -> segment map (context scratch)
-    uint64_t tile_map_cap;
     uint32_t *copy_tickets; // the copies' range-tail counters (copy.hip): in the context's
                             // geometry the ring's first line, in a launch's copy its own line
     int copy_steal;         // 1: range tails from the counters (default), 0: off
@@ -155,12 +150,6 @@ hipError_t launch_encode_acl_grp(const honu_meta *meta, const honu_acl *acl, uin
 hipError_t launch_encode_acl_grp_self(const honu_meta *meta, const honu_acl *acl, const uint64_t *payload_off,
                                       uint64_t n, uint8_t *out, uint64_t out_cap, const uint64_t *out_off,
                                       int32_t *status, int max_blocks, hipStream_t s);
-// header + Metadata tail, ACL entries included, one record per 16-lane group
-// (enc.hip; encode_variant 1, A/B build only)
-hipError_t launch_encode_tail_grp(const honu_meta *meta, const uint8_t *var, const honu_acl *acl,
-                                  const uint32_t *reg, const uint64_t *payload_off, uint64_t n,
-                                  uint8_t *out, uint64_t out_cap, const uint64_t *out_off,
-                                  int32_t *status, int max_blocks, hipStream_t s);
 
 hipError_t launch_encode_sizes_grp(const honu_meta *meta, uint64_t var_len, const honu_acl *acl,
                                    uint64_t acl_len, const uint32_t *reg, uint64_t reg_len,

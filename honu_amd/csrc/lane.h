@@ -114,14 +114,25 @@ template <int NDW> struct RowT {
 };
 using Row = RowT<88>;
 
-// lani.Decoder (lani/decode.go) over [tstart, end) for one lane.
-struct LaneDec {
+// A decoder's bytes from global memory: u8(p) and fetch16(p, end, lo, hi), as
+// the LDS window's (win.h LaneWin).
+struct GlobalSrc {
     const uint8_t *base;
+    HONU_DEV uint32_t u8(uint64_t p) const { return base[p]; }
+    HONU_DEV void fetch16(uint64_t p, uint64_t end, uint64_t &lo, uint64_t &hi) const {
+        lane_fetch16(base, p, end, lo, hi);
+    }
+};
+
+// lani.Decoder (lani/decode.go) over [tstart, end) for one lane, its bytes
+// from Src.
+template <class Src> struct DecT {
+    Src src;
     uint64_t p, end, tstart;
 
     HONU_DEV int u8(uint32_t &v) {  // DecodeByte :94-103
         if (p >= end) return HONU_ERR_EOF;
-        v = base[p];
+        v = src.u8(p);
         p += 1;
         return HONU_OK;
     }
@@ -135,7 +146,7 @@ struct LaneDec {
         const uint64_t avail = end - p;
         const uint32_t n = avail < maxw ? (uint32_t)avail : maxw;
         uint64_t lo, hi;
-        lane_fetch16(base, p, end, lo, hi);
+        src.fetch16(p, end, lo, hi);
         const uint32_t k = uvarint_window(lo, hi, n, v);
         if (!k) return err;
         p += k;
@@ -157,7 +168,7 @@ struct LaneDec {
     HONU_DEV int ulid(uint64_t &lo, uint64_t &hi) {  // DecodeULID :209-221
         if (p >= end) return HONU_ERR_EOF;
         if (p + 16 > end) return HONU_ERR_UNEXPECTED_EOF;
-        lane_fetch16(base, p, end, lo, hi);
+        src.fetch16(p, end, lo, hi);
         p += 16;
         return HONU_OK;
     }
@@ -180,10 +191,7 @@ struct LaneDec {
         return HONU_OK;
     }
 };
-
-}  // namespace honu
-
-namespace honu {
+using LaneDec = DecT<GlobalSrc>;
 
 // binary.PutUvarint of x as little-endian bytes: lo = bytes 0..7, hi = bytes
 // 8..9; returns the length (1..10). Branch-free LEB128 expansion (the inverse
@@ -410,7 +418,6 @@ static __device__ uint64_t g_enc_stamps[1 << 16][ENC_STAMPS];  // per translatio
 // encode of one record by one lane (object.go:24-45, metadata.go:108-200),
 // shared by the split kernels (lane.hip) and the fused kernel (fused.hip)
 // ------------------------------------------------------------------------
-HONU_DEV uint64_t frame_len(uint64_t len) { return uvarint_len(len) + len; }
 HONU_DEV uint64_t ld64(const uint8_t *p) { return *reinterpret_cast<const uint64_t *>(p); }
 
 // The list kernel (k_encode_acl_grp) writes an all-present ACL list's whole

@@ -13,7 +13,6 @@
 
 namespace honu {
 
-#define GO_MAX_ALLOC (1ull << 48)  // runtime maxAlloc, linux/amd64
 #define COFF(f) ((int)offsetof(honu_collection, f))
 
 using CRow = RowT<92>;
@@ -21,10 +20,9 @@ using CRow = RowT<92>;
 HONU_DEV bool sys_span_in(honu_span s, uint64_t var_len) {
     return s.len == 0 || (s.off <= var_len && s.len <= var_len - s.off);
 }
-HONU_DEV uint64_t sys_frame_len(uint64_t len) { return uvarint_len(len) + len; }
 
 // Field.Encode (field.go:42-60) length
-HONU_DEV uint64_t field_len(honu_span name) { return sys_frame_len(name.len) + 1 + 16; }
+HONU_DEV uint64_t field_len(honu_span name) { return frame_len(name.len) + 1 + 16; }
 
 // ------------------------------------------------------------------------
 // encode size pass: 1 + EncodeStruct(collection) + 1
@@ -61,7 +59,7 @@ HONU_DEV void system_size_one(uint64_t i, const honu_collection *__restrict__ ro
         if (!x.present) continue;
         ok = sys_span_in(x.name, var_len) && (!x.has_field || sys_span_in(x.field_name, var_len)) &&
              (!x.has_ref || sys_span_in(x.ref_name, var_len));
-        t += 16 + sys_frame_len(x.name.len) + 1 + 2;
+        t += 16 + frame_len(x.name.len) + 1 + 2;
         if (x.has_field) t += field_len(x.field_name);
         if (x.has_ref) t += field_len(x.ref_name);
     }
@@ -70,7 +68,7 @@ HONU_DEV void system_size_one(uint64_t i, const honu_collection *__restrict__ ro
         if (status) status[i] = HONU_ERR_INPUT;
         return;
     }
-    t += 1 + 16 + sys_frame_len(c.name.len);  // struct flag, ID, Name
+    t += 1 + 16 + frame_len(c.name.len);  // struct flag, ID, Name
     t += 1;                                   // Version flag
     if (pr & HONU_HAS_VERSION)
         t += uvarint_len(c.pid) + uvarint_len(c.vid) + uvarint_len(c.region) + 1 +
@@ -83,13 +81,13 @@ HONU_DEV void system_size_one(uint64_t i, const honu_collection *__restrict__ ro
     for (uint64_t k = 0; k < nr; k++) t += uvarint_len(reg[c.regions_off + k]);
     t += 4;  // Publisher, Schema, Encryption, Compression flags
     if (pr & HONU_HAS_PUBLISHER)
-        t += 32 + sys_frame_len(c.ip_address.len) + sys_frame_len(c.user_agent.len);
+        t += 32 + frame_len(c.ip_address.len) + frame_len(c.user_agent.len);
     if (pr & HONU_HAS_SCHEMA)
-        t += sys_frame_len(c.schema_name.len) + uvarint_len(c.schema_major) +
+        t += frame_len(c.schema_name.len) + uvarint_len(c.schema_major) +
              uvarint_len(c.schema_minor) + uvarint_len(c.schema_patch);
     if (pr & HONU_HAS_ENCRYPTION)
-        t += sys_frame_len(c.public_key_id.len) + sys_frame_len(c.encryption_key.len) +
-             sys_frame_len(c.hmac_secret.len) + sys_frame_len(c.signature.len) + 3;
+        t += frame_len(c.public_key_id.len) + frame_len(c.encryption_key.len) +
+             frame_len(c.hmac_secret.len) + frame_len(c.signature.len) + 3;
     if (pr & HONU_HAS_COMPRESSION) t += 1 + uvarint_len(zigzag(c.compression_level));
     t += 1 + uvarint_len(nx);  // Flags, len(Indexes)
     t += uvarint_len(zigzag(c.created)) + uvarint_len(zigzag(c.modified));
@@ -310,7 +308,7 @@ HONU_DEV void system_parse_one(uint64_t i, const uint8_t *__restrict__ rec,
         st = HONU_ERR_PANIC;  // obj[1 : len(obj)-1] out of range (system.go:40)
     } else {
         LaneDec D;
-        D.base = rec;
+        D.src.base = rec;
         D.tstart = t0;
         D.p = t0;
         D.end = t1;
@@ -464,7 +462,7 @@ HONU_DEV void system_fill_one(uint64_t i, const uint8_t *__restrict__ rec,
     }
     const DecodeScratch sc = scratch[i];
     LaneDec D;
-    D.base = rec;
+    D.src.base = rec;
     D.end = sc.rec_end;
     D.tstart = 0;
     uint32_t f = 0, u = 0;

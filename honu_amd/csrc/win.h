@@ -26,8 +26,6 @@
 
 namespace honu {
 
-#define GO_MAX_ALLOC (1ull << 48)  // runtime maxAlloc, linux/amd64
-
 // The pad slot of every window (slot 16, there for bank spreading) holds a
 // copy of ring slot 0, so a 16-byte field read is five aligned dword reads
 // with no wrap and four v_alignbyte, not two 16-byte reads and a per-lane
@@ -162,70 +160,7 @@ struct LaneWin {
     }
 };
 
-struct WDec {  // lani.Decoder (lani/decode.go) over [tstart, end), as LaneDec
-    const LaneWin *w;
-    uint64_t p, end, tstart;
-
-    HONU_DEV int u8(uint32_t &v) {  // DecodeByte :94-103
-        if (p >= end) return HONU_ERR_EOF;
-        v = w->u8(p);
-        p += 1;
-        return HONU_OK;
-    }
-    HONU_DEV int boolean(uint32_t &v) {  // DecodeBool :105-120
-        int st = u8(v);
-        if (st) return st;
-        return v > 1 ? HONU_ERR_PARSE_BOOLEAN : HONU_OK;
-    }
-    HONU_DEV int uv(uint32_t maxw, int err, uint64_t &v) {
-        if (p >= end) return HONU_ERR_EOF;
-        const uint64_t avail = end - p;
-        const uint32_t n = avail < maxw ? (uint32_t)avail : maxw;
-        uint64_t lo, hi;
-        w->fetch16(p, end, lo, hi);
-        const uint32_t k = uvarint_window(lo, hi, n, v);
-        if (!k) return err;
-        p += k;
-        return HONU_OK;
-    }
-    HONU_DEV int u32(uint32_t &v) {  // DecodeUint32 :127-146
-        uint64_t x = 0;
-        int st = uv(5, HONU_ERR_PARSE_VARINT, x);
-        v = (uint32_t)x;
-        return st;
-    }
-    HONU_DEV int u64(uint64_t &v) { return uv(10, HONU_ERR_PARSE_VARINT, v); }  // :149-168
-    HONU_DEV int i64(int64_t &v) {                                             // :171-190
-        uint64_t x = 0;
-        int st = uv(10, HONU_ERR_PARSE_VARINT, x);
-        v = unzigzag(x);
-        return st;
-    }
-    HONU_DEV int ulid(uint64_t &lo, uint64_t &hi) {  // DecodeULID :209-221
-        if (p >= end) return HONU_ERR_EOF;
-        if (p + 16 > end) return HONU_ERR_UNEXPECTED_EOF;
-        w->fetch16(p, end, lo, hi);
-        p += 16;
-        return HONU_OK;
-    }
-    HONU_DEV int frame(uint64_t &off, uint64_t &len) {  // Decode :30-56, readLength :261-282
-        uint64_t rl = 0;
-        int st = uv(10, HONU_ERR_NO_LENGTH, rl);
-        if (st) return st;
-        if (rl >= (1ull << 63)) return HONU_ERR_PANIC;  // int(rl) < 0 -> makeslice
-        if (rl == 0) {
-            off = 0;
-            len = 0;
-            return HONU_OK;
-        }
-        if (rl > (uint64_t)INT64_MAX - (p - tstart)) return HONU_ERR_PANIC;  // d.i + rl overflows
-        if (p + rl > end) return HONU_ERR_UNEXPECTED_EOF;
-        off = p;
-        len = rl;
-        p += rl;
-        return HONU_OK;
-    }
-};
+using WDec = DecT<const LaneWin &>;  // the walk's decoder reads through the lane's window
 
 #define HONU_SKIP 0x7fffffff  // lane without a walk (past n)
 
@@ -441,11 +376,8 @@ HONU_DEV void win_walk(uint64_t i0, uint8_t *wave_smem, const uint8_t *__restric
     else if (!v1) st = HONU_ERR_BAD_VERSION;
     else if (d < 0) st = HONU_ERR_MALFORMED;
     else if (!in_range) st = HONU_ERR_PANIC;  // o[1+d+b:]
-    WDec D;
-    D.w = &W;
-    D.end = end;
-    D.tstart = st == HONU_OK ? beg + 1 + (uint64_t)b + (uint64_t)d : 0;
-    D.p = D.tstart;
+    const uint64_t tstart = st == HONU_OK ? beg + 1 + (uint64_t)b + (uint64_t)d : 0;
+    WDec D{W, tstart, end, tstart};
     WSTAMP(2);  // header read
     W.refill(st == HONU_OK ? win_base(D.p) : NOWIN);
     WSTAMP(3);  // first window

@@ -276,17 +276,16 @@ int32_t honu_ctx_reset(honu_ctx *ctx, void *stream);
  * workgroups of the one-wave-per-record kernels, default 8 per CU),
  * "lane_blocks" (cap on workgroups of the lane, group and window kernels;
  * default 0 = no cap — a cap leaves room for a concurrent payload copy),
- * "copy_variant" (copy-engine variant, default 0), "copy_steal" (1, the
+ * "copy_variant" (kept for compatibility: 0 only), "copy_steal" (1, the
  * default: in a copy whose payloads average >= 16 KB each streaming wave
  * copies 7/8 of its byte range, then the ranges' last eighths from a counter
  * in the context; 0: fixed ranges only), "record_variant" (how the
  * per-record metadata kernels map records to lanes: 0 auto — the fastest
  * measured form per kernel, with honu_decode_batch running the single-launch
  * decode for batches of 48 K records or more; 5 the split decode at every
- * size; 6 the single-launch decode at every size), "encode_variant" (the
- * header/tail encoder of honu_encode_records: 0 one record per lane + the ACL
- * lists by 16-lane groups, the default; 1 one record per 16-lane group laid
- * out by a prefix sum over the grammar's slots, same bytes), "speculate" (the
+ * size; 6 the single-launch decode at every size), "encode_variant" (kept for
+ * compatibility: 0 only, one record per lane + the ACL lists by 16-lane
+ * groups), "speculate" (the
  * single-launch decode's speculation, see honu_decode_records: 2 auto, the
  * default — only in materialising calls and the table forms, where it hides
  * look-back waits; 1 in every call; 0 off), "speculate_backoff" (0..16: the calls left without

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Sweep the payload-copy launch geometry / variants on one chunk of records
+"""Sweep the payload-copy launch geometry on one chunk of records
 (interleaved rounds in one process; GB/s = 2 x payload bytes / kernel time)."""
 import argparse
 import json
@@ -23,7 +23,6 @@ def main():
     ap.add_argument("--shape", default="large")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--blocks", default="1,2,4,8")
-    ap.add_argument("--variants", default="0,6,7")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     codec = Codec(0, a.records)
@@ -62,13 +61,12 @@ def main():
                                     cap // 16, P(data), total + 16 * n, P(tot), s), "tables")
     torch.cuda.synchronize()
     nbytes = 2 * int(off[n])
-    cfgs = [(b, v) for b in map(int, a.blocks.split(",")) for v in map(int, a.variants.split(","))]
+    cfgs = list(map(int, a.blocks.split(",")))
     res = {cfg: ([], []) for cfg in cfgs}
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
     for _ in range(a.rounds):
-        for (b, v) in cfgs:
+        for b in cfgs:
             _lib.check(L.honu_ctx_set_param(c, b"copy_blocks", b * ncu), "p")
-            _lib.check(L.honu_ctx_set_param(c, b"copy_variant", v), "p")
             for k, fn in enumerate((
                 lambda: L.honu_encode_payloads(c, P(pay), P(do), n, P(out), out.numel(), P(out_off), P(st), s),
                 lambda: L.honu_decode_payloads(c, P(out), n, P(dinfo), P(data), P(tot), s))):
@@ -77,7 +75,7 @@ def main():
                 _lib.check(fn(), "copy")
                 e1.record()
                 torch.cuda.synchronize()
-                res[(b, v)][k].append(nbytes / (e0.elapsed_time(e1) / 1e3) / 1e9)
+                res[b][k].append(nbytes / (e0.elapsed_time(e1) / 1e3) / 1e9)
     # memcpy reference of the same byte count
     x = torch.empty(int(off[n]), dtype=torch.uint8, device=dev)
     ref = []
@@ -89,8 +87,8 @@ def main():
         torch.cuda.synchronize()
         ref.append(nbytes / (e0.elapsed_time(e1) / 1e3) / 1e9)
     rows = []
-    for (b, v), (enc, dec) in res.items():
-        rows.append({"blocks_per_cu": b, "variant": v, "enc_med": statistics.median(enc),
+    for b, (enc, dec) in res.items():
+        rows.append({"blocks_per_cu": b, "enc_med": statistics.median(enc),
                      "dec_med": statistics.median(dec), "enc_max": max(enc), "dec_max": max(dec)})
     rows.sort(key=lambda r: -(r["enc_med"] + r["dec_med"]))
     for r in rows:
