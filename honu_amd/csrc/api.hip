@@ -23,19 +23,13 @@ struct honu_ctx {
     DecodeScratch *scratch;  // max_n
     uint32_t *reg_inline;    // 8 * max_n: region ids handed from the group parse to fill
     EncAclPos *enc_acl;      // max_n: ACL list hand-over, lane encoder -> group ACL encoder
-    // decoupled look-back state of the fused decode (fused.hip): a
-    // ticket/epoch block and 3 status words per 64-record tile
-    LbState *lb_dec;
-    uint64_t *lb_dec_status;
-    uint64_t *lb_dec_gstatus;  // the group words, after the tile words (same epoch scheme)
-    uint64_t lb_dec_words;     // tile + group words
-    uint64_t lb_bytes;       // the look-back blocks + status words, from lb_dec
+    FusedState dec;          // look-back state of the fused decode (fused.hip)
+    uint64_t lb_bytes;       // the look-back blocks + status words + copy counters, from dec.lb
     ScanState scan;          // look-back state of the one-launch scans (scan.hip)
     // speculation back-off (fused.hip): a guarded recovery launch that ran sets
-    // *spec_seen (pinned host word, written by the device); the next call sees
-    // it and decodes SPEC_BACKOFF_CALLS calls without speculation, so a stream
+    // *dec.spec_seen (pinned host words, written by the device); the next call
+    // sees it and decodes SPEC_BACKOFF_CALLS calls without speculation, so a stream
     // of batches with malformed records pays ~1.1x instead of ~2x per batch
-    uint32_t *spec_seen;     // pinned: [0] the back-off flag, [1] recovery launches run (a count)
     uint32_t spec_off;       // calls left without speculation
     int speculate;           // honu_ctx_set_param("speculate"): 0 off, 1 on, 2 where it hides a wait
     // honu_encode_records: the ACL lists' kernel on a stream of the context's
@@ -46,7 +40,6 @@ struct honu_ctx {
     int enc_fork;            // honu_ctx_set_param("encode_fork", 0 off / 1 on / 2 auto: when lane_blocks caps the grid)
     bool acl_inplace;        // honu_ctx_set_param("acl_inplace"): decode returns all-present ACL lists in place
     bool reg_inplace;        // honu_ctx_set_param("regions_inplace"): decode returns region lists in place
-    bool inline_recovery;    // honu_ctx_set_param("inline_recovery"): ticket-form launches recover in-launch
     int guard_blocks;        // honu_ctx_set_param("guard_blocks"): one-wave workgroups of the guarded launch
                              // (0: as many as the speculative launch has waves)
     uint32_t copy_seq;       // copy calls issued: call k takes counter line k % COPY_TICKET_LINES
@@ -100,6 +93,40 @@ static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)
 static int fused_blocks(const LaunchGeom &g) {
     const int resident = 2 * g.num_cu;
     return g.lane_blocks > 0 && g.lane_blocks < resident ? g.lane_blocks : resident;
+}
+
+// p: count elements at byte offset `at` of base; returns the offset after them
+template <class T>
+static uint64_t carve(T *&p, void *base, uint64_t at, uint64_t count) {
+    p = (T *)((uintptr_t)base + at);
+    return at + count * sizeof(T);
+}
+
+// The context's workspace laid out in order from base; returns the end offset.
+// A null base gives the bytes to allocate (the pointers are then not for use).
+// From dec.lb to the end: what a clean look-back state zeroes (lb_bytes).
+static uint64_t ctx_carve(honu_ctx *c, void *base) {
+    const uint64_t n = c->max_n;
+    const uint64_t tiles = (n + HONU_WAVE - 1) / HONU_WAVE;
+    // 3 status words per tile, then 3 per 64-tile group (lookback.h
+    // lb_resolve_grouped*)
+    const uint64_t groups = (tiles / HONU_WAVE + 1) > LB_GROUPS ? tiles / HONU_WAVE + 1 : LB_GROUPS;
+    uint64_t at = 0;
+    at = carve(c->counts, base, at, 3 * n);
+    at = carve(c->offs, base, at, 3 * n);
+    at = carve(c->totals, base, at, 4);
+    at = carve(c->scratch, base, at, n);
+    at = carve(c->reg_inline, base, at, 8 * n);
+    at = carve(c->enc_acl, base, at, n);
+    at = carve(c->dec.lb, base, at, 1);
+    at = carve(c->scan.lb, base, at, 1);
+    at = carve(c->dec.status, base, at, 3 * tiles);
+    at = carve(c->dec.gstatus, base, at, 3 * groups);  // (the same epoch scheme as the tile words)
+    c->dec.words = 3 * tiles + 3 * groups;
+    c->scan.words = scan_status_words(n);
+    at = carve(c->scan.status, base, at, c->scan.words);
+    // the copies' range-tail counters: a ring of 128-byte lines
+    return carve(c->geom.copy_tickets, base, at, (uint64_t)COPY_TICKET_LINES * COPY_TICKET_STRIDE);
 }
 
 // A stream with a CU mask or a non-default priority: honu_encode_records then
@@ -200,7 +227,7 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
         if (c->ev_join) (void)hipEventDestroy(c->ev_join);
         if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
         if (c->aux) (void)hipStreamDestroy(c->aux);
-        if (c->spec_seen) (void)hipHostFree(c->spec_seen);
+        if (c->dec.spec_seen) (void)hipHostFree(c->dec.spec_seen);
         if (c->ws) (void)hipFree(c->ws);
         free(c);
         *err = e;
@@ -217,37 +244,22 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
         c->geom.record_variant = 0;
     c->acl_inplace = env_int("HONU_ACL_INPLACE", 1) != 0;
     c->reg_inplace = env_int("HONU_REGIONS_INPLACE", 1) != 0;
-    // measured slower than the guarded launch (1M Small zero copy 0.56 ->
-    // 0.67-0.70 ms, the Small step 4.17-4.21 -> 4.26-4.42 ms; DESIGN §3
-    // "Round 5"): off by default
-    c->inline_recovery = env_int("HONU_INLINE_RECOVERY", 0) != 0;
     c->guard_blocks = env_int("HONU_GUARD_BLOCKS", 0);
     if (c->guard_blocks < 0) c->guard_blocks = 0;
-    const uint64_t n = c->max_n;
-    const uint64_t tiles = (n + HONU_WAVE - 1) / HONU_WAVE;
-    const uint64_t scan_words = scan_status_words(n);
-    // 3 status words per tile, then 3 per 64-tile group (lookback.h
-    // lb_resolve_grouped*)
-    const uint64_t groups = (tiles / HONU_WAVE + 1) > LB_GROUPS ? tiles / HONU_WAVE + 1 : LB_GROUPS;
-    const uint64_t lb_dec_words = 3 * tiles + 3 * groups;
-    // (+ the copies' range-tail counters: a ring of 128-byte lines)
-    const uint64_t lb_bytes =
-        2 * sizeof(LbState) + 8 * (lb_dec_words + scan_words) + COPY_TICKET_LINES * 4 * COPY_TICKET_STRIDE;
-    const uint64_t bytes = 8 * (3 * n + 3 * n + 4) + sizeof(DecodeScratch) * n + 32 * n +
-                           sizeof(EncAclPos) * n + lb_bytes + 256;
+    const uint64_t end = ctx_carve(c, nullptr), bytes = end + 256;
     if (hipMalloc(&c->ws, bytes) != hipSuccess) {
         c->ws = nullptr;
         char msg[96];
         snprintf(msg, sizeof msg, "hipMalloc(%llu) failed", (unsigned long long)bytes);
         return fail(HONU_E_HIP, msg);
     }
-    if (hipHostMalloc((void **)&c->spec_seen, 2 * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent) !=
-        hipSuccess) {
-        c->spec_seen = nullptr;
+    if (hipHostMalloc((void **)&c->dec.spec_seen, 2 * sizeof(uint32_t),
+                      hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+        c->dec.spec_seen = nullptr;
         return fail(HONU_E_HIP, "hipHostMalloc(spec_seen) failed");
     }
-    c->spec_seen[0] = 0;
-    c->spec_seen[1] = 0;
+    c->dec.spec_seen[0] = 0;
+    c->dec.spec_seen[1] = 0;
     c->speculate = SPECULATE_DEFAULT;
     c->enc_fork = env_int("HONU_ENCODE_FORK", 2);
     if (c->enc_fork < 0 || c->enc_fork > 2) c->enc_fork = 2;
@@ -263,32 +275,15 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
         c->ev_join = nullptr;
         return fail(HONU_E_HIP, "event creation failed");
     }
-    uint64_t *w = (uint64_t *)c->ws;
-    c->counts = w;
-    w += 3 * n;
-    c->offs = w;
-    w += 3 * n;
-    c->totals = w;
-    w += 4;
-    c->scratch = (DecodeScratch *)w;
-    c->reg_inline = (uint32_t *)(c->scratch + n);
-    c->enc_acl = (EncAclPos *)(c->reg_inline + 8 * n);
-    c->lb_dec = (LbState *)(c->enc_acl + n);
-    c->scan.lb = c->lb_dec + 1;
-    c->lb_dec_status = (uint64_t *)(c->scan.lb + 1);
-    c->lb_dec_words = lb_dec_words;
-    c->lb_dec_gstatus = c->lb_dec_status + 3 * tiles;
-    c->scan.status = c->lb_dec_status + c->lb_dec_words;
-    c->scan.words = scan_words;
-    c->geom.copy_tickets = (uint32_t *)(c->scan.status + scan_words);
+    ctx_carve(c, c->ws);
+    c->lb_bytes = (uint64_t)((uint8_t *)c->ws + end - (uint8_t *)c->dec.lb);
     c->geom.copy_steal = 1;
     c->scan.max_blocks = 4 * prop.multiProcessorCount;
-    c->lb_bytes = lb_bytes;
     // clean look-back state: epoch 0 with no published tile. On a stream of
     // the call's own, so work other contexts have in flight keeps running.
     hipStream_t s = nullptr;
     bool ok = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipMemsetAsync(c->lb_dec, 0, lb_bytes, s) == hipSuccess;
+    ok = ok && hipMemsetAsync(c->dec.lb, 0, c->lb_bytes, s) == hipSuccess;
     ok = ok && hipStreamSynchronize(s) == hipSuccess;
     if (s) (void)hipStreamDestroy(s);
     if (!ok) return fail(HONU_E_HIP, "look-back state initialisation failed");
@@ -298,7 +293,7 @@ honu_ctx *honu_ctx_create(int device, uint64_t max_records, int32_t *err) {
 int32_t honu_ctx_reset(honu_ctx *ctx, void *stream) {
     if (!ctx) return arg_fail("ctx");
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemsetAsync(ctx->lb_dec, 0, ctx->lb_bytes, (hipStream_t)stream));
+    HIPCHK(hipMemsetAsync(ctx->dec.lb, 0, ctx->lb_bytes, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     return HONU_OK;
 }
@@ -311,7 +306,7 @@ void honu_ctx_destroy(honu_ctx *ctx) {
     (void)hipEventDestroy(ctx->ev_join);
     (void)hipStreamDestroy(ctx->aux);
     (void)hipFree(ctx->ws);
-    (void)hipHostFree(ctx->spec_seen);
+    (void)hipHostFree(ctx->dec.spec_seen);
     free(ctx);
 }
 
@@ -326,15 +321,15 @@ int32_t honu_ctx_set_param(honu_ctx *ctx, const char *name, int64_t value) {
     else if (!strcmp(name, "encode_fork") && value >= 0 && value <= 2) ctx->enc_fork = (int)value;
     else if (!strcmp(name, "acl_inplace") && (value == 0 || value == 1)) ctx->acl_inplace = value != 0;
     else if (!strcmp(name, "regions_inplace") && (value == 0 || value == 1)) ctx->reg_inplace = value != 0;
-    else if (!strcmp(name, "inline_recovery") && (value == 0 || value == 1)) ctx->inline_recovery = value != 0;
     else if (!strcmp(name, "guard_blocks") && value >= 0 && value <= 65536) ctx->guard_blocks = (int)value;
     else if (!strcmp(name, "speculate_backoff") && value >= 0 && value <= (int64_t)SPEC_BACKOFF_CALLS) {
-        __atomic_store_n(ctx->spec_seen, 0u, __ATOMIC_RELAXED);
+        __atomic_store_n(ctx->dec.spec_seen, 0u, __ATOMIC_RELAXED);
         ctx->spec_off = (uint32_t)value;
     }
     else if (!strcmp(name, "copy_steal") && (value == 0 || value == 1)) ctx->geom.copy_steal = (int)value;
-    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant")) {
-        // kept for compatibility: there is one copy engine and one header/tail encoder, form 0
+    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant") || !strcmp(name, "inline_recovery")) {
+        // kept for compatibility: there is one copy engine, one header/tail encoder and one
+        // recovery form (the guarded launch), each form 0
         if (value != 0) return arg_fail(name);
     }
     else if (!strcmp(name, "record_variant") &&
@@ -354,14 +349,14 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "encode_fork")) *value = ctx->enc_fork;
     else if (!strcmp(name, "acl_inplace")) *value = ctx->acl_inplace ? 1 : 0;
     else if (!strcmp(name, "regions_inplace")) *value = ctx->reg_inplace ? 1 : 0;
-    else if (!strcmp(name, "inline_recovery")) *value = ctx->inline_recovery ? 1 : 0;
     else if (!strcmp(name, "guard_blocks")) *value = ctx->guard_blocks;
     else if (!strcmp(name, "recoveries"))  // recovery launches that ran, since the context was created
-        *value = __atomic_load_n(ctx->spec_seen + 1, __ATOMIC_RELAXED);
+        *value = __atomic_load_n(ctx->dec.spec_seen + 1, __ATOMIC_RELAXED);
     else if (!strcmp(name, "speculate_backoff"))  // calls the next call starts without speculation
-        *value = __atomic_load_n(ctx->spec_seen, __ATOMIC_RELAXED) ? SPEC_BACKOFF_CALLS : ctx->spec_off;
+        *value = __atomic_load_n(ctx->dec.spec_seen, __ATOMIC_RELAXED) ? SPEC_BACKOFF_CALLS : ctx->spec_off;
     else if (!strcmp(name, "copy_steal")) *value = ctx->geom.copy_steal;
-    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant")) *value = 0;  // (see set_param)
+    else if (!strcmp(name, "copy_variant") || !strcmp(name, "encode_variant") || !strcmp(name, "inline_recovery"))
+        *value = 0;  // (see set_param)
     else if (!strcmp(name, "record_variant")) *value = ctx->geom.record_variant;
     else if (!strcmp(name, "walk_flag_checks")) *value = decode_walk_flag_checks();  // read only: the build's
     else if (!strcmp(name, "sort_tile")) *value = sort_tile();  // read only: keys per workgroup per sort pass
@@ -628,8 +623,8 @@ int32_t honu_decode_records(honu_ctx *ctx, const uint8_t *d_rec, const uint64_t 
     }
     // speculation back-off: a recovery of an earlier call has finished (the
     // word is read without waiting: a recovery still in flight is seen later)
-    if (__atomic_load_n(ctx->spec_seen, __ATOMIC_RELAXED)) {
-        __atomic_store_n(ctx->spec_seen, 0u, __ATOMIC_RELAXED);
+    if (__atomic_load_n(ctx->dec.spec_seen, __ATOMIC_RELAXED)) {
+        __atomic_store_n(ctx->dec.spec_seen, 0u, __ATOMIC_RELAXED);
         ctx->spec_off = SPEC_BACKOFF_CALLS;
     }
     // speculation hides the look-back wait; a zero-copy call with both list
@@ -640,12 +635,10 @@ int32_t honu_decode_records(honu_ctx *ctx, const uint8_t *d_rec, const uint64_t 
     const bool hides = materialize || !ctx->acl_inplace || !ctx->reg_inplace;
     const bool spec = (ctx->speculate == 1 || (ctx->speculate == 2 && hides)) && ctx->spec_off == 0;
     if (ctx->spec_off) ctx->spec_off--;
-    HIPCHK(launch_decode_fused(d_rec, d_rec_off, n, d_meta, d_info, d_acl, acl_cap, d_regions,
-                               regions_cap, materialize != 0, data_cap, ctx->scratch, ctx->offs,
-                               tot, ctx->lb_dec, ctx->lb_dec_status, ctx->lb_dec_gstatus,
-                               ctx->lb_dec_words, fused_blocks(ctx->geom), ctx->spec_seen,
-                               ctx->spec_seen + 1, spec, ctx->acl_inplace, ctx->reg_inplace, ctx->inline_recovery,
-                               ctx->guard_blocks, s));
+    const DecodeOut O{d_meta,   d_info,           d_acl,        acl_cap,   d_regions, regions_cap,
+                      data_cap, materialize != 0, ctx->scratch, ctx->offs, tot,       ctx->reg_inplace};
+    const FusedOpts opt{fused_blocks(ctx->geom), ctx->guard_blocks, spec, ctx->acl_inplace};
+    HIPCHK(launch_decode_fused(d_rec, d_rec_off, n, O, ctx->dec, opt, s));
     return HONU_OK;
 }
 

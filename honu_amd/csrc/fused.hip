@@ -21,21 +21,8 @@ namespace honu {
 // decode: Object.Metadata() + Data() + Tombstone() + StorageVersion()
 // (object.go:47-134), lani walk metadata.go:202-302, tables and offsets.
 // Columns: 0 ACL entries, 1 regions, 2 16-byte aligned payload bytes.
+// The outputs: DecodeOut (kernels.h).
 // ------------------------------------------------------------------------
-struct DecodeOut {
-    honu_meta *meta;
-    honu_record_info *info;
-    honu_acl *acl;
-    uint64_t acl_cap;
-    uint32_t *reg;
-    uint64_t reg_cap;
-    uint64_t data_cap;
-    int materialize;          // data offsets into a data arena (else zero-copy)
-    DecodeScratch *scratch;   // materialize: payload sources for honu_decode_payloads
-    uint64_t *offs;           // materialize: offs[3i+2] = data arena offset
-    uint64_t *totals;         // column totals (3)
-    bool reg_inplace;         // region lists returned in place (HONU_REGIONS_INPLACE)
-};
 
 // Launches of at least this many tiles speculate (publish + ACL flags, below)
 // and are followed by the guarded launch: with the flag gather gone the
@@ -81,13 +68,9 @@ static_assert(STAGE_SLOTS % HONU_WAVE == 0, "whole instructions");
 // parity green, 62 K Large 0.076-0.080 vs 0.077-0.080 ms, 64 K / 40 K / 16 K
 // Small equal, profiles/r04/ab/dec_pair_fill_ab.jsonl.)
 enum { FORM_TICKET = 0, FORM_STATIC = 1 };
-template <bool B> struct BoolC { static constexpr bool value = B; };
-template <int FORM> constexpr uint32_t form_slots() { return STAGE_SLOTS; }
 // a wave's LDS: its windows during the walk, the staging after it
-template <int FORM> constexpr uint32_t form_wave_bytes() {
-    return form_slots<FORM>() * 16 + 32 > WIN_WAVE_BYTES ? form_slots<FORM>() * 16 + 32 : WIN_WAVE_BYTES;
-}
-static_assert(2 * HONU_WAVES_PER_BLOCK * form_wave_bytes<FORM_STATIC>() + 64 <= 160 * 1024, "2 workgroups per CU");
+constexpr uint32_t FUSED_WAVE_BYTES = STAGE_SLOTS * 16 + 32 > WIN_WAVE_BYTES ? STAGE_SLOTS * 16 + 32 : WIN_WAVE_BYTES;
+static_assert(2 * HONU_WAVES_PER_BLOCK * FUSED_WAVE_BYTES + 64 <= 160 * 1024, "2 workgroups per CU");
 
 template <uint32_t SLOTS>
 struct AclStage {
@@ -313,25 +296,6 @@ struct SpecPub {
 // totals (lookback.h); each form a kernel of its own, so none pays another's
 // registers or LDS.
 //
-// In-launch recovery (ticket form, MODE 1 with `inline_rec`): instead of a
-// guarded second launch, the speculative launch itself finishes the job. A
-// wave whose ticket loop ends counts its tiles into LbState::tdone and waits
-// until every tile of the pass is counted (the tiles it waits for are held
-// by running waves: tickets are only taken by running waves, so this cannot
-// deadlock, also when the grid is not resident at once); misspec is final
-// then. Clean (the usual case): the wave ends. Misspeculated: every wave
-// releases its stores (agent scope: the pass-1 stores of the same outputs,
-// maybe from another XCD, must land after them), counts its tiles into
-// rdone, and once all are released the waves decode the batch again without
-// speculation from a second ticket counter, with look-back words tagged as
-// pass 1 (lookback.h). No second launch waits for CU resources behind other
-// kernels (a no-op guard of 78 KB workgroups spent up to
-// 1.4 ms queued beside the bench's copies and encoder; the guard is now
-// k_decode_guard below). Measured slower in the clean case, so off. Static
-// tiles keep the guarded launch: their waves may wait on workgroups that are
-// not resident yet, so a launch-wide wait could deadlock beside another
-// persistent kernel.
-//
 // The recovery count (a measurement, honu_ctx_get_param "recoveries") in the
 // context's pinned word: one thread of one wave updates it per recovery, so a
 // plain load and store, no read-modify-write atomic over PCIe (which needs
@@ -347,33 +311,30 @@ template <int MODE, int FORM, bool INPL, int WPB>
 HONU_DEV void decode_fused_body(
     const uint8_t *__restrict__ rec, const uint64_t *__restrict__ rec_off, uint64_t n,
     DecodeOut O, LbState *lb, uint64_t *lb_status, uint64_t *lb_gstatus, uint64_t lb_words,
-    uint32_t *spec_seen, uint32_t *recoveries, bool inline_rec) {
-    constexpr int mode = MODE;
-    if (mode == 2 && __hip_atomic_load(&lb->misspec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
+    uint32_t *spec_seen, uint32_t *recoveries) {
+    if (MODE == 2 && __hip_atomic_load(&lb->misspec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0)
         return;  // every wave of the launch returns: the look-back state is untouched
     // a recovery that runs tells the host (the context's pinned word), which
     // then decodes the context's next calls without speculation (api.hip)
-    if (mode == 2 && spec_seen && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (MODE == 2 && spec_seen && blockIdx.x == 0 && threadIdx.x == 0) {
         __hip_atomic_store(spec_seen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         count_recovery(recoveries);  // (a count apart from the back-off flag, for measurements)
     }
     constexpr bool STAT = FORM != FORM_TICKET;
-    constexpr uint32_t WAVE_BYTES = form_wave_bytes<FORM>();
-    __shared__ __attribute__((aligned(16))) uint8_t smem[WPB * WAVE_BYTES];
+    constexpr bool spec = MODE == 1;  // speculative publish and ACL flags
+    __shared__ __attribute__((aligned(16))) uint8_t smem[WPB * FUSED_WAVE_BYTES];
     __shared__ uint32_t last_flag;
     __shared__ uint32_t wg_ticket;
-    uint8_t *ws = smem + (threadIdx.x / HONU_WAVE) * WAVE_BYTES;
+    uint8_t *ws = smem + (threadIdx.x / HONU_WAVE) * FUSED_WAVE_BYTES;
     const uint32_t lane = lane_id();
-    const uint32_t ep = lb_epoch(lb);
+    const uint32_t ep = lb_epoch(lb);  // the tag of this launch's look-back words
     const uint64_t ntiles = (n + HONU_WAVE - 1) / HONU_WAVE;
-    const bool ir = MODE == 1 && FORM == FORM_TICKET && inline_rec;  // in-launch recovery
     const uint64_t waves = (uint64_t)gridDim.x * WPB;
     // every tile has a resident wave of its own: static tiles (lookback.h)
     // (measured: taking the next ticket and loading its bounds before the
     // look-back wait, to overlap them with it, doubled the wait: tiles are
     // then handed out ~40 us before their waves start them, which spreads the
     // publish times of consecutive tiles)
-    constexpr bool stat_idx = STAT;
     uint64_t k_static = (uint64_t)blockIdx.x * WPB + threadIdx.x / HONU_WAVE;
     WSTAMP_START();
     // ticket mode: the next tile's ticket is requested once the current tile's
@@ -385,7 +346,7 @@ HONU_DEV void decode_fused_body(
     // Large 0.258 -> 0.238 ms, profiles/r03/ab/wg_ticket_ab.jsonl).
     uint32_t tk = 0;
     bool tk_pending = false;
-    if constexpr (!stat_idx) {  // the same in every wave of the workgroup
+    if constexpr (!STAT) {  // the same in every wave of the workgroup
         if (threadIdx.x == 0)
             wg_ticket = __hip_atomic_fetch_add(&lb->ticket, (uint32_t)WPB, __ATOMIC_RELAXED,
                                                __HIP_MEMORY_SCOPE_AGENT);
@@ -393,31 +354,18 @@ HONU_DEV void decode_fused_body(
         tk = wg_ticket + threadIdx.x / HONU_WAVE;
         tk_pending = true;
     }
-    uint32_t my_tiles = 0;  // tiles of pass 0 this wave decoded
-    // one pass over the tiles; SPEC (compile time): speculative publish and
-    // ACL flags (mode 1's first pass), so each pass is specialised
-    auto tiles = [&](auto spec_c, uint32_t pass) {
-    constexpr bool spec = decltype(spec_c)::value;
-    const uint32_t tag = pass ? (ep | LB_PASS_BIT) : ep;  // look-back words of this pass
-    uint32_t *tctr = pass ? &lb->ticket2 : &lb->ticket;
     for (;;) {
         uint64_t t;
-        if constexpr (stat_idx) {
+        if constexpr (STAT) {
             t = k_static;
             k_static += waves;
         } else if (tk_pending) {
             t = __builtin_amdgcn_readlane(tk, 0);
             tk_pending = false;
         } else {
-            t = lb_ticket(tctr);
+            t = lb_ticket(lb);
         }
         if (t >= ntiles) break;
-        if (pass == 0) my_tiles++;
-        // the recovery pass tells the host (once: the wave holding its first tile)
-        if (pass == 1 && t == 0 && spec_seen && lane == 0) {
-            __hip_atomic_store(spec_seen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            count_recovery(recoveries);
-        }
         const uint64_t i0 = t * HONU_WAVE, i = i0 + lane;
         const uint64_t lim = i0 + HONU_WAVE < n ? i0 + HONU_WAVE : n;  // the tile's records are [i0, lim)
         const bool valid = i < lim;
@@ -431,7 +379,7 @@ HONU_DEV void decode_fused_body(
         early.spec_acl = early.on;
         early.status = lb_status;
         early.t = t;
-        early.ep = tag;
+        early.ep = ep;
         win_walk(i0, ws, rec, lim, H, R, P, early, INPL, O.reg_inplace);
 
         // counts -> offsets: wave scan + look-back across tiles
@@ -452,14 +400,14 @@ HONU_DEV void decode_fused_body(
             x2 = wave_excl(c2, agg[2]);
             // publish, then write the rows while the predecessors finish
             // (their list offsets are patched in below)
-            lb_publish<3>(lb_status, t, tag, agg);
+            lb_publish<3>(lb_status, t, ep, agg);
         }
         rows_out<true>(ws, R, i0, lim, O.meta);
         // table form (acl_inplace 0): the ACL lists with every entry present
         // go to the table from LDS; the first round of their blocks is staged
         // now, before the wait, as it needs no offsets
         const bool fl = !INPL && valid && P.st == HONU_OK && P.ntab && (P.acl_pos & GRP_ACL_FAST);
-        AclStage<form_slots<FORM>()> S;
+        AclStage<STAGE_SLOTS> S;
         S.init(fl, P.acl_pos & GRP_POS_MASK, P.ntab);
         if (S.more()) S.issue(ws, rec);
         // in-place form: a speculated list stays where it is, but its entry
@@ -497,16 +445,16 @@ HONU_DEV void decode_fused_body(
         // segment start (copy.hip DecodeSegments).
         const bool need = t == ntiles - 1 || agg[0] || agg[1] || O.materialize;
         if constexpr (STAT)  // every tile runs at once: grouped prefixes (lookback.h)
-            lb_resolve_grouped<3>(lb_status, lb_gstatus, t, ntiles, tag, agg, excl, need);
+            lb_resolve_grouped<3>(lb_status, lb_gstatus, t, ntiles, ep, agg, excl, need);
         else  // tickets: a decoupled look-back over the group totals (the plain
               // one over tile words, lb_resolve, measured 3 % slower on 1M Small)
-            lb_resolve_grouped_lb<3>(lb_status, lb_gstatus, t, ntiles, tag, agg, excl, need);
+            lb_resolve_grouped_lb<3>(lb_status, lb_gstatus, t, ntiles, ep, agg, excl, need);
         if (!need) excl[0] = excl[1] = excl[2] = 0;  // (offsets of zero entries: unused)
         WSTAMP(11);  // look-back wait
         // nothing is staged in the in-place form: the next ticket is requested
         // here, and the rest of the tile hides its round trip
-        if (!stat_idx && igather) {
-            tk = lb_ticket_issue(tctr);
+        if (!STAT && igather) {
+            tk = lb_ticket_issue(lb);
             tk_pending = true;
         }
         if (t == ntiles - 1 && lane < 3)
@@ -602,8 +550,8 @@ HONU_DEV void decode_fused_body(
         while (S.more()) {
             const bool last = S.stop >= S.nbtot;  // wave-uniform
             acl_bad |= S.store(ws, O.acl, ao, ok, early.spec_acl, [&]() {
-                if (last && !stat_idx) {
-                    tk = lb_ticket_issue(tctr);
+                if (last && !STAT) {
+                    tk = lb_ticket_issue(lb);
                     tk_pending = true;
                 }
             });
@@ -620,38 +568,15 @@ HONU_DEV void decode_fused_body(
             __hip_atomic_store(&lb->misspec, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         WSTAMP(13);  // ACL fill
     }
-    };  // tiles
-    tiles(BoolC<MODE == 1>{}, 0u);
-    if constexpr (MODE == 1 && FORM == FORM_TICKET) {
-        if (ir) {
-            // in-launch recovery (above): the speculative pass is over for
-            // this wave; its misspec store (sc1) has completed before its
-            // tiles are counted
-            __builtin_amdgcn_s_waitcnt(0);
-            if (lane == 0) __hip_atomic_fetch_add(&lb->tdone, my_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            lb_wait_count(&lb->tdone, ntiles);
-            uint32_t ms = 0;
-            if (lane == 0) ms = __hip_atomic_load(&lb->misspec, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__builtin_amdgcn_readlane(ms, 0)) {  // misspeculated (else: done)
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // pass-0 stores reach memory
-                if (lane == 0)
-                    __hip_atomic_fetch_add(&lb->rdone, my_tiles, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                lb_wait_count(&lb->rdone, ntiles);
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                tk_pending = false;
-                tiles(BoolC<false>{}, 1u);
-            }
-        }
-    }
     WSTAMP_FLUSH();
-    lb_finish_blocks(lb, lb_status, lb_words, gridDim.x, &last_flag, mode == 2 || ir);
+    lb_finish_blocks(lb, lb_status, lb_words, gridDim.x, &last_flag, MODE == 2);
 }
 
 #define HONU_FUSED_PARAMS                                                                             \
     const uint8_t *__restrict__ rec, const uint64_t *__restrict__ rec_off, uint64_t n, DecodeOut O,   \
         LbState *lb, uint64_t *lb_status, uint64_t *lb_gstatus, uint64_t lb_words, uint32_t *spec_seen, \
-        uint32_t *recoveries, bool inline_rec
-#define HONU_FUSED_ARGS rec, rec_off, n, O, lb, lb_status, lb_gstatus, lb_words, spec_seen, recoveries, inline_rec
+        uint32_t *recoveries
+#define HONU_FUSED_ARGS rec, rec_off, n, O, lb, lb_status, lb_gstatus, lb_words, spec_seen, recoveries
 
 template <int MODE, int FORM, bool INPL>
 __global__ __launch_bounds__(HONU_BLOCK, 2) void k_decode_fused(HONU_FUSED_PARAMS) {
@@ -670,6 +595,16 @@ template <bool INPL>
 __global__ __launch_bounds__(HONU_WAVE) void k_decode_guard(
     HONU_FUSED_PARAMS) {
     decode_fused_body<2, FORM_TICKET, INPL, 1>(HONU_FUSED_ARGS);
+}
+
+// The kernel of a launch: stat, every tile a resident wave (FORM_STATIC).
+using FusedKernel = void (*)(HONU_FUSED_PARAMS);
+template <int MODE>
+static FusedKernel fused_kernel(bool stat, bool inplace) {
+    if (stat && inplace) return k_decode_fused<MODE, FORM_STATIC, true>;
+    if (stat) return k_decode_fused<MODE, FORM_STATIC, false>;
+    if (inplace) return k_decode_fused<MODE, FORM_TICKET, true>;
+    return k_decode_fused<MODE, FORM_TICKET, false>;
 }
 
 #ifdef HONU_STAGE_TIMING
@@ -692,14 +627,16 @@ extern "C" int32_t honu_debug_stage_times(void *host, uint64_t waves, int32_t re
 // tests know which nil entries cost a recovery launch.
 int decode_walk_flag_checks() { return (HONU_GATHER_SKIP_WIN ? 1 : 0) | (HONU_GATHER_SKIP_WIN2 ? 2 : 0); }
 
+// One recovery form, the guarded launch. Measured and not kept (source in git
+// history, commit c7b102b, behind a context param; DESIGN_HISTORY §3 "Round
+// 5"): in-launch recovery for ticket launches, where a speculative
+// launch waited launch-wide for its own tiles and, misspeculated, decoded the
+// batch again in a second pass over a second ticket counter, its look-back
+// words told apart by a pass bit in the tag. No guard then waits for CU
+// resources, but the clean case paid: 1M Small zero copy 0.556-0.566 ->
+// 0.669-0.698 ms, the Small step 4.17-4.21 -> 4.26-4.42 ms.
 hipError_t launch_decode_fused(const uint8_t *rec, const uint64_t *rec_off, uint64_t n,
-                               honu_meta *meta, honu_record_info *info, honu_acl *acl,
-                               uint64_t acl_cap, uint32_t *reg, uint64_t reg_cap, int materialize,
-                               uint64_t data_cap, DecodeScratch *scratch, uint64_t *offs,
-                               uint64_t *totals, LbState *lb, uint64_t *lb_status,
-                               uint64_t *lb_gstatus, uint64_t lb_words, int max_blocks, uint32_t *spec_seen,
-                               uint32_t *recoveries, bool allow_spec, bool inplace, bool reg_inplace,
-                               bool inline_rec, int guard_blocks, hipStream_t s) {
+                               const DecodeOut &O, const FusedState &F, const FusedOpts &opt, hipStream_t s) {
     if (n == 0) return hipSuccess;
     // (32-record tiles for batches whose 64-record tiles fill at most half the
     // resident waves, so that every SIMD walks records, measured slower with
@@ -708,51 +645,29 @@ hipError_t launch_decode_fused(const uint8_t *rec, const uint64_t *rec_off, uint
     // sets a short batch's time. DESIGN §3 "Round 4".)
     const uint64_t tiles = (n + HONU_WAVE - 1) / HONU_WAVE;
     uint64_t b = (tiles + HONU_WAVES_PER_BLOCK - 1) / HONU_WAVES_PER_BLOCK;
-    if (max_blocks > 0 && b > (uint64_t)max_blocks) b = (uint64_t)max_blocks;
-    DecodeOut O{meta, info, acl, acl_cap, reg, reg_cap, data_cap, materialize, scratch, offs, totals, reg_inplace};
+    if (opt.max_blocks > 0 && b > (uint64_t)opt.max_blocks) b = (uint64_t)opt.max_blocks;
     // speculation pays where tiles queue for tickets (1M Small 0.866 -> 0.840
     // ms with the publish alone, -> 0.778 with the ACL flags too) and, since
     // the flag gather is gone, in static-tile launches of ~1000 tiles and more
     // (profiles/r03/fused_spec_ab.jsonl, spec_acl_ab*.jsonl)
     const bool stat = tiles <= b * HONU_WAVES_PER_BLOCK && tiles <= (uint64_t)HONU_WAVE * LB_GROUPS;
-    const dim3 grid((unsigned)b), block(HONU_BLOCK);
-#define HONU_FUSED_LAUNCH_F(M, F, I)                                                                      \
-    hipLaunchKernelGGL((k_decode_fused<M, F, I>), grid, block, 0, s, rec, rec_off, n, O, lb, lb_status,    \
-                       lb_gstatus, lb_words, spec_seen, recoveries, inline_rec && !stat)
-#define HONU_FUSED_LAUNCH(M)                                                                               \
-    do {                                                                                                   \
-        if (stat && inplace) HONU_FUSED_LAUNCH_F(M, FORM_STATIC, true);                                     \
-        else if (stat) HONU_FUSED_LAUNCH_F(M, FORM_STATIC, false);                                          \
-        else if (inplace) HONU_FUSED_LAUNCH_F(M, FORM_TICKET, true);                                        \
-        else HONU_FUSED_LAUNCH_F(M, FORM_TICKET, false);                                                    \
-    } while (0)
-    if (tiles < FUSED_SPEC_MIN_TILES || !allow_spec) {
-        HONU_FUSED_LAUNCH(0);
-        return hipGetLastError();
-    }
-    // speculative launch, then (static tiles, or inline recovery off) the
-    // guarded recovery launch (a no-op unless a record failed after publishing
-    // its counts or a speculated ACL list holds a nil entry)
-    HONU_FUSED_LAUNCH(1);
-    if (stat || !inline_rec) {
-        // one-wave workgroups, as many waves as the speculative launch had
-        // (guard_blocks > 0: that many), ticket tiles whatever the batch
-        // (deadlock-free with any grid, static or not)
-        uint64_t gw = b * HONU_WAVES_PER_BLOCK;
-        if (guard_blocks > 0 && (uint64_t)guard_blocks < gw) gw = (uint64_t)guard_blocks;
-        const dim3 g2((unsigned)gw), b2(HONU_WAVE);
-        if (inplace)
-            hipLaunchKernelGGL((k_decode_guard<true>), g2, b2, 0, s, rec, rec_off, n, O, lb, lb_status,
-                               lb_gstatus, lb_words, spec_seen, recoveries, false);
-        else
-            hipLaunchKernelGGL((k_decode_guard<false>), g2, b2, 0, s, rec, rec_off, n, O, lb, lb_status,
-                               lb_gstatus, lb_words, spec_seen, recoveries, false);
-    }
-#undef HONU_FUSED_LAUNCH_F
-#undef HONU_FUSED_LAUNCH
+    const bool spec = opt.speculate && tiles >= FUSED_SPEC_MIN_TILES;
+    auto launch = [&](FusedKernel k, uint64_t blocks, unsigned threads) {
+        hipLaunchKernelGGL(k, dim3((unsigned)blocks), dim3(threads), 0, s, rec, rec_off, n, O, F.lb, F.status,
+                           F.gstatus, F.words, F.spec_seen, F.spec_seen + 1);
+    };
+    launch(spec ? fused_kernel<1>(stat, opt.acl_inplace) : fused_kernel<0>(stat, opt.acl_inplace), b, HONU_BLOCK);
+    if (!spec) return hipGetLastError();
+    // every speculative launch is followed by the guarded recovery launch (a
+    // no-op unless a record failed after publishing its counts or a speculated
+    // ACL list holds a nil entry): one-wave workgroups, as many waves as the
+    // speculative launch had (guard_blocks > 0: that many), ticket tiles
+    // whatever the batch (deadlock-free with any grid, static or not)
+    uint64_t gw = b * HONU_WAVES_PER_BLOCK;
+    if (opt.guard_blocks > 0 && (uint64_t)opt.guard_blocks < gw) gw = (uint64_t)opt.guard_blocks;
+    launch(opt.acl_inplace ? k_decode_guard<true> : k_decode_guard<false>, gw, HONU_WAVE);
     return hipGetLastError();
 }
-
 
 #undef OFF
 

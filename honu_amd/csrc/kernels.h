@@ -6,12 +6,6 @@
 #include "common.h"
 #include "lookback.h"
 
-// LDS budget per wave for the Metadata tail writer (encode.hip) and the
-// decode window (decode.hip). Generated tails are 0.15-1.8 KB; longer tails
-// take the in-place fallback (encode) or re-stage the window (decode).
-#define ENC_TAIL_LDS 4096
-#define DEC_WIN 2048
-
 namespace honu {
 
 // Per-record scratch handed from honu_decode_parse to honu_decode_fill.
@@ -100,8 +94,7 @@ struct LaunchGeom {
     int record_variant;     // per-record kernels: 0 auto (the fastest measured form
                             // of each; honu_decode_batch single-launch from 48 K
                             // records), 5 split decode, 6 single-launch decode
-                            // at every size (the rejected one-record-per-wave /
-                            // per-group / per-lane forms 1-4: DESIGN §3)
+                            // at every size
     int seek_variant;       // honu_key_seek: 0 auto (by the probe and row counts), 1 the direct
                             // binary search, 2 the fenced one (seek.hip)
     uint32_t *copy_tickets; // the copies' range-tail counters (copy.hip): in the context's
@@ -165,14 +158,37 @@ hipError_t launch_decode_fill_grp(const uint8_t *rec, uint64_t n, honu_meta *met
 // fused.hip: one launch from records to rows, record info and tables
 // (materialize: also the data-arena offsets honu_decode_payloads copies to)
 int decode_walk_flag_checks();  // fused.hip: bit 0 window 1's flags, bit 1 window 2's
+struct DecodeOut {
+    honu_meta *meta;
+    honu_record_info *info;
+    honu_acl *acl;
+    uint64_t acl_cap;
+    uint32_t *reg;
+    uint64_t reg_cap;
+    uint64_t data_cap;
+    int materialize;          // data offsets into a data arena (else zero-copy)
+    DecodeScratch *scratch;   // materialize: payload sources for honu_decode_payloads
+    uint64_t *offs;           // materialize: offs[3i+2] = data arena offset
+    uint64_t *totals;         // column totals (3)
+    bool reg_inplace;         // region lists returned in place (HONU_REGIONS_INPLACE)
+};
+// The context's look-back state of the launch (lookback.h): the ticket/epoch
+// block, 3 status words per 64-record tile, then 3 per 64-tile group (words:
+// both), and the pinned host words the guarded launch writes.
+struct FusedState {
+    LbState *lb;
+    uint64_t *status, *gstatus;
+    uint64_t words;
+    uint32_t *spec_seen;  // [0] the back-off flag, [1] recoveries (a count)
+};
+struct FusedOpts {
+    int max_blocks;    // cap on the launch's workgroups (0: none)
+    int guard_blocks;  // one-wave workgroups of the guarded launch (0: as many as the launch has waves)
+    bool speculate;    // launches of FUSED_SPEC_MIN_TILES tiles and more speculate
+    bool acl_inplace;  // all-present ACL lists returned in place (HONU_ACL_INPLACE)
+};
 hipError_t launch_decode_fused(const uint8_t *rec, const uint64_t *rec_off, uint64_t n,
-                               honu_meta *meta, honu_record_info *info, honu_acl *acl,
-                               uint64_t acl_cap, uint32_t *reg, uint64_t reg_cap, int materialize,
-                               uint64_t data_cap, DecodeScratch *scratch, uint64_t *offs,
-                               uint64_t *totals, LbState *lb, uint64_t *lb_status,
-                               uint64_t *lb_gstatus, uint64_t lb_words, int max_blocks, uint32_t *spec_seen,
-                               uint32_t *recoveries, bool allow_spec, bool inplace, bool reg_inplace,
-                               bool inline_rec, int guard_blocks, hipStream_t s);
+                               const DecodeOut &O, const FusedState &F, const FusedOpts &opt, hipStream_t s);
 
 hipError_t launch_decode_parse_win(const uint8_t *rec, const uint64_t *rec_off, uint64_t n,
                                    honu_meta *meta, honu_record_info *info,

@@ -307,13 +307,11 @@ int32_t honu_ctx_reset(honu_ctx *ctx, void *stream);
  * and the single-launch decode's 64-record tiles then need no offsets from
  * their predecessors (only the batch's last tile resolves them, for
  * d_totals).
- * "inline_recovery" (0 default, 1 on): a speculative single-launch decode
- * with more 64-record tiles than resident waves redoes a misspeculated batch
- * inside the same launch instead of in a guarded second launch (one-wave
- * workgroups, placed as registers free up beside other kernels even when it
- * has nothing to do); launches whose tiles all fit keep the guarded launch. Measured slower
- * in the common, clean case (DESIGN §3 "Round 5"), hence off. "recoveries"
- * (get only): the recovery passes or launches the context has run. */
+ * "inline_recovery" (kept for compatibility: 0 only): a misspeculated
+ * single-launch decode is always redone by the guarded second launch; redoing
+ * it inside the speculative launch measured slower in the common, clean case
+ * and is gone. "recoveries" (get only): the recovery launches the context has
+ * run. */
 int32_t honu_ctx_set_param(honu_ctx *ctx, const char *name, int64_t value);
 
 /* The current value of a parameter of honu_ctx_set_param, and

@@ -335,8 +335,8 @@ def test_long_tails_and_nil_entries_parity(codec, oracle_lib):
 
 
 @pytest.mark.parametrize("lens", ["tiny", "edges", "skew", "long", "mixed"])
-@pytest.mark.parametrize("copy_variant", [0, -1, 1, 6, 11],
-                         ids=["default", "steal_off", "unroll8", "sweep", "nt_load"])
+@pytest.mark.parametrize("copy_variant", [0, -1, 6, 11],
+                         ids=["default", "steal_off", "sweep", "nt_load"])
 def test_copy_engine_parity(oracle_lib, copy_variant, lens):
     """The payload copy engine on awkward length mixes: payloads of 0-40 bytes
     (head/tail bytes only), lengths around multiples of 16, and a skewed mix of
@@ -346,9 +346,9 @@ def test_copy_engine_parity(oracle_lib, copy_variant, lens):
     average >= 64 KB, so the short-segment class and the range tails at
     once). The default copy and, "steal_off", the copy with the context param
     copy_steal 0. Encoded bytes and materialised payloads are bit-exact.
-    ("unroll8", "sweep", "nt_load": retired copy variants, which no build has
-    any more; the library refuses them and the cases skip, as they always did
-    on the product library. They go with a later change.)"""
+    ("sweep", "nt_load": retired copy variants, which no build has any more;
+    the library refuses them and the cases skip, as they always did on the
+    product library. They go with a later change.)"""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     rng = np.random.default_rng(5)
@@ -743,16 +743,17 @@ def test_environment_is_ignored(oracle_lib, monkeypatch):
 
 
 def test_retired_variant_params_accept_only_zero():
-    """The params "copy_variant" and "encode_variant" stay in the ABI for callers
-    that read or set them, but the library has one copy engine and one
-    header/tail encoder: get gives 0, set takes 0 and refuses 1 with
+    """The params "copy_variant", "encode_variant" and "inline_recovery" stay in
+    the ABI for callers that read or set them, but the library has one copy
+    engine, one header/tail encoder and one recovery form (the guarded
+    launch): get gives 0, set takes 0 and refuses 1 with
     HONU_E_ARG, leaving 0. The same in the product and the A/B build; no
     kernel is launched."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     c = hobj.Codec(0, 16)
     try:
-        for name in (b"copy_variant", b"encode_variant"):
+        for name in (b"copy_variant", b"encode_variant", b"inline_recovery"):
             v = ctypes.c_int64(-1)
             assert c.lib.honu_ctx_get_param(c.ctx, name, ctypes.byref(v)) == 0 and v.value == 0, name
             assert c.lib.honu_ctx_set_param(c.ctx, name, 0) == 0, name

@@ -279,11 +279,10 @@ def test_speculative_publish_recovers(oracle_lib, n, bad, inplace):
         c.close()
 
 
-@pytest.mark.parametrize("inline_rec,guard_blocks", [(1, 0), (0, 0), (0, 16)],
-                         ids=["in_launch", "guard_launch", "small_guard"])
+@pytest.mark.parametrize("guard_blocks", [0, 16], ids=["guard_launch", "small_guard"])
 @FORMS
 @pytest.mark.parametrize("n,k", [(140000, 1), (140000, 200), (100000, 1), (100000, 200)])
-def test_speculative_acl_flags_recover(oracle_lib, n, k, inplace, inline_rec, guard_blocks):
+def test_speculative_acl_flags_recover(oracle_lib, n, k, inplace, guard_blocks):
     """Speculative launches also take every ACL list that fits its record as
     all present without gathering its entry flags in the walk; the table fill
     (table form) or the flag gather after the publish (in-place form, fused.hip
@@ -291,11 +290,10 @@ def test_speculative_acl_flags_recover(oracle_lib, n, k, inplace, inline_rec, gu
     then read every later field at the wrong place) are spliced into a
     2188-tile batch (ticket tiles) or a 1563-tile one (static tiles): the check
     must raise misspec and the batch be decoded again, bit-exact with the
-    oracle, by the guarded second launch (inline_recovery 0, the default), by
-    a guarded launch of 16 one-wave workgroups (guard_blocks 16: ticket
-    tiles over 16 waves, also after a static speculative launch), or by the launch's own
-    recovery pass (inline_recovery 1; static tiles keep the guard); a clean
-    batch decoded next on the same context is exact too."""
+    oracle, by the guarded second launch (the default) or by a guarded launch
+    of 16 one-wave workgroups (guard_blocks 16: ticket tiles over 16 waves,
+    also after a static speculative launch); a clean batch decoded next on the
+    same context is exact too."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from corpora import random_metas
@@ -305,7 +303,6 @@ def test_speculative_acl_flags_recover(oracle_lib, n, k, inplace, inline_rec, gu
     c = hobj.Codec(0, n)
     try:
         _speculative(c)
-        hobj._lib.check(c.lib.honu_ctx_set_param(c.ctx, b"inline_recovery", inline_rec), "param")
         hobj._lib.check(c.lib.honu_ctx_set_param(c.ctx, b"guard_blocks", guard_blocks), "param")
         r0 = _get(c, b"recoveries")
         d = _Dec(c, brec, boff, inplace)
