@@ -788,6 +788,49 @@ func (c *Codec) SeekKeys(o *KeyOrder, probes [][]byte, info devBuf) ([]Seek, err
 	return out, nil
 }
 
+// MergeKeys is a batch of Puts into an ordered bucket (collections.Put,
+// store.go:232, 395; collectionsBucket.Put, store.go:530; the bkt.Put(k, value)
+// calls of iterator/cursor_test.go:235): the stable merge of a resident sorted
+// order with a sorted batch, both from SortKeys or an earlier MergeKeys. The
+// result is what SortKeys returns for the keys of a followed by the keys of b:
+// b's record indices are its own plus a's count, equal keys stay one run with
+// a's records before b's, and the run's last record, Seek.Latest, is the
+// latest arrival, where bbolt's Put of a stored key replaces its value. a and
+// b are not changed and stay the caller's to Free. The result takes SeekKeys,
+// Has, Exists and a further MergeKeys; it holds no key column of its own, so
+// KeyObjects is for an order that SortKeys made.
+//
+// UNCOMPILED, like the rest of this file. honu_key_merge is exercised on the
+// GPU from Python (tests/test_gpu_key_merge.py), graph capture included.
+func (c *Codec) MergeKeys(a, b *KeyOrder) (*KeyOrder, error) {
+	n := a.n + b.n
+	if n > 0xFFFFFFFF {
+		return nil, fmt.Errorf("%d keys: an order indexes at most 2^32 - 1", n)
+	}
+	o := &KeyOrder{n: n}
+	o.order, o.sorted, o.valid = device(uintptr(4*n)), device(uintptr(C.HONU_KEY_LEN*n)), device(8)
+	hOrder, hValid := pinned(uintptr(4*n)), pinned(8)
+	defer hOrder.free()
+	defer hValid.free()
+	for _, s := range []C.int32_t{
+		C.honu_key_merge(c.ctx, (*C.uint8_t)(a.sorted.p), (*C.uint32_t)(a.order.p), (*C.uint64_t)(a.valid.p),
+			C.uint64_t(a.n), (*C.uint8_t)(b.sorted.p), (*C.uint32_t)(b.order.p), (*C.uint64_t)(b.valid.p),
+			C.uint64_t(b.n), C.uint32_t(a.n), (*C.uint8_t)(o.sorted.p), (*C.uint32_t)(o.order.p),
+			(*C.uint64_t)(o.valid.p), c.stream),
+		C.honu_memcpy_d2h(hOrder.p, o.order.p, C.uint64_t(4*n), c.stream),
+		C.honu_memcpy_d2h(hValid.p, o.valid.p, 8, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_key_merge", s); err != nil {
+			o.Free()
+			return nil, err
+		}
+	}
+	o.Order = append([]uint32(nil), unsafe.Slice((*uint32)(hOrder.p), n)...)
+	o.Valid = *(*uint64)(hValid.p)
+	return o, nil
+}
+
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&
 // bytes.HasPrefix(key, probe) of the key Seek lands on.
 func (c *Codec) Has(o *KeyOrder, probes [][]byte) ([]bool, error) {

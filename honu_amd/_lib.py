@@ -55,6 +55,7 @@ _PROTOS = {
     "honu_key_objects": (I32, [P, P, P, P, U64, P, P, P, P, U64, P]),
     "honu_sizeof_seek": (U64, []),
     "honu_key_seek": (I32, [P, P, P, U64, P, P, C.c_uint32, U64, P, P, P, P]),
+    "honu_key_merge": (I32, [P, P, P, P, U64, P, P, P, U64, C.c_uint32, P, P, P, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -364,6 +364,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "seek_fence")) *value = seek_fence();  // read only: keys of the fenced seek's LDS stage
     else if (!strcmp(name, "seek_auto_probes")) *value = (int64_t)seek_auto_probes();  // read only: what
     else if (!strcmp(name, "seek_auto_keys")) *value = (int64_t)seek_auto_keys();      // "seek_variant" 0 picks by
+    else if (!strcmp(name, "merge_tile")) *value = merge_tile();  // read only: output positions per workgroup of the merge
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -798,6 +799,28 @@ int32_t honu_key_seek(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_seek(ctx->geom.seek_variant, ctx->geom.num_cu, d_sorted, d_valid, n, d_probes,
                            d_probe_status, probe_len, m, d_order, d_info, d_out, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a batch of Puts into the sorted column (store.go:232, 395, 530)
+// ---------------------------------------------------------------------------
+int32_t honu_key_merge(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t *d_order_a,
+                       const uint64_t *d_valid_a, uint64_t na, const uint8_t *d_sorted_b,
+                       const uint32_t *d_order_b, const uint64_t *d_valid_b, uint64_t nb, uint32_t b_base,
+                       uint8_t *d_sorted_out, uint32_t *d_order_out, uint64_t *d_valid_out, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (na > 0xFFFFFFFFull || nb > 0xFFFFFFFFull || na + nb > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    if ((uint64_t)b_base + nb > 0xFFFFFFFFull) return arg_fail("b_base + nb above 2^32 - 1");
+    if (!d_valid_a || !d_valid_b || !d_valid_out) return arg_fail("null valid count");
+    if ((na && !d_sorted_a) || (nb && !d_sorted_b) || (na + nb && !d_sorted_out)) return arg_fail("null column");
+    if (d_order_out && (!d_order_a || !d_order_b)) return arg_fail("d_order_out needs both input orders");
+    if (!aligned(d_order_a, 4) || !aligned(d_order_b, 4) || !aligned(d_order_out, 4) || !aligned(d_valid_a, 8) ||
+        !aligned(d_valid_b, 8) || !aligned(d_valid_out, 8))
+        return arg_fail("orders 4-byte / valid counts 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_merge(d_sorted_a, d_order_a, d_valid_a, na, d_sorted_b, d_order_b, d_valid_b, nb, b_base,
+                            d_sorted_out, d_order_out, d_valid_out, (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -267,6 +267,14 @@ hipError_t launch_key_seek(int variant, int num_cu, const uint8_t *sorted, const
                            const uint8_t *probes, const int32_t *pstatus, uint32_t probe_len, uint64_t m,
                            const uint32_t *order, const honu_record_info *info, honu_seek *out, hipStream_t s);
 
+// merge.hip: a batch of Puts (store.go:232, 395, 530) into the sorted column: the stable
+// merge of two of launch_sort_keys' outputs, A first on equal keys. na + nb <= 2^32 - 1;
+// order == null merges the column alone
+uint32_t merge_tile();
+hipError_t launch_key_merge(const uint8_t *sa, const uint32_t *oa, const uint64_t *valid_a, uint64_t na,
+                            const uint8_t *sb, const uint32_t *ob, const uint64_t *valid_b, uint64_t nb,
+                            uint32_t b_base, uint8_t *out, uint32_t *order, uint64_t *valid_out, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

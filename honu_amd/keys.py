@@ -10,7 +10,9 @@ GPU is Codec.sort_keys / Codec.key_objects (object.py, honu_sort_keys and
 honu_key_objects in include/honu_codec.h). seek() and has() are the host
 statement of Cursor.Seek (iterator/cursor.go:44-55) and Collection.Has
 (collection.go:47-51) over such a sorted list; the batch form is
-Codec.seek_keys (honu_key_seek).
+Codec.seek_keys (honu_key_seek). merge() is the host statement of a batch of
+Puts into such a list (store.go:232, 395, 530); the batch form is
+Codec.merge_keys (honu_key_merge).
 """
 from __future__ import annotations
 
@@ -123,6 +125,32 @@ def seek(sorted_keys: Sequence[bytes], probe: bytes):
     nxt = _prefix_successor(probe)
     end = len(sorted_keys) if nxt is None else bisect.bisect_left(sorted_keys, nxt, lo=pos)
     return pos, end
+
+
+def merge(a: Sequence[bytes], b: Sequence[bytes]) -> List[bytes]:
+    """A batch of Puts into an ordered bucket (collections.Put, store.go:232,
+    395; collectionsBucket.Put, store.go:530; the bkt.Put(k, value) calls of
+    iterator/cursor_test.go:235), after which Cursor.Seek
+    (iterator/cursor.go:44-55) and Collection.Has (collection.go:47-51) see
+    the new keys: the stable merge of two sorted lists of keys by
+    bytes.Compare, which is Python's order of bytes. On equal keys a's come
+    before b's and each side keeps its own order, so a key's run ends on its
+    latest arrival: bbolt's Put of a stored key replaces its value, and
+    position end - 1 of seek() is the row that holds it. The rows returned are
+    the objects given, not copies. The batch form on the GPU is
+    Codec.merge_keys (honu_key_merge in include/honu_codec.h)."""
+    out: List[bytes] = []
+    i = j = 0
+    while i < len(a) and j < len(b):
+        if a[i] <= b[j]:
+            out.append(a[i])
+            i += 1
+        else:
+            out.append(b[j])
+            j += 1
+    out.extend(a[i:])
+    out.extend(b[j:])
+    return out
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

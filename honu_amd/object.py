@@ -335,6 +335,30 @@ class Codec:
             probe_len, m, _lib.ptr(order), _lib.ptr(info), _lib.ptr(out), self.stream), "honu_key_seek")
         return out[:20 * m].view(_torch().int32).view(m, 5)
 
+    def merge_keys(self, sorted_a, order_a, valid_a, sorted_b, order_b, valid_b, b_base: Optional[int] = None):
+        """A batch of Puts into the sorted column (store.go:232, 395, 530):
+        the stable merge of two of sort_keys' outputs (sorted column, order,
+        valid count, all on the device), A first on equal keys, with b_base
+        (default: A's row count) added to B's record indices. Returns (sorted
+        column, order as an int32 view or None when either input order is
+        None, valid count as one int64), on the device: what sort_keys returns
+        for the concatenated columns, so it feeds seek_keys, key_objects and
+        a further merge_keys."""
+        na, nb = sorted_a.numel() // 29, sorted_b.numel() // 29
+        if b_base is None:
+            b_base = na
+        with_order = order_a is not None and order_b is not None
+        out = self._empty(29 * (na + nb))
+        order = self._empty(4 * (na + nb)) if with_order else None
+        valid = self._empty(8)
+        _lib.check(self.lib.honu_key_merge(
+            self.ctx, _lib.ptr(sorted_a), _lib.ptr(order_a) if with_order else 0, _lib.ptr(valid_a), na,
+            _lib.ptr(sorted_b), _lib.ptr(order_b) if with_order else 0, _lib.ptr(valid_b), nb, b_base,
+            _lib.ptr(out), _lib.ptr(order), _lib.ptr(valid), self.stream), "honu_key_merge")
+        torch = _torch()
+        return (out[:29 * (na + nb)], order[:4 * (na + nb)].view(torch.int32) if with_order else None,
+                valid[:8].view(torch.int64))
+
 
 _default: Optional[Codec] = None
 

@@ -19,6 +19,7 @@
  *   sort.Sort(keys.Keys)        keys/keys.go:126-130   honu_sort_keys (stable order of the column)
  *   an object's versions        keys/keys.go:73-92     honu_key_objects (ranges of the order, latest)
  *   Cursor.Seek, Has, Exists    iterator/cursor.go:44-55  honu_key_seek (positions of a batch of probes)
+ *   bucket.Put (a batch)        store.go:232, 395, 530 honu_key_merge (stable merge into the sorted column)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -641,6 +642,54 @@ int32_t honu_key_seek(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_
                       const uint8_t *d_probes, const int32_t *d_probe_status, uint32_t probe_len,
                       uint64_t m, const uint32_t *d_order, const honu_record_info *d_info,
                       honu_seek *d_out, void *stream);
+
+/* A batch of Puts into the sorted key column: what collections.Put(key, data)
+ * (store.go:232, 395), collectionsBucket.Put(collectionKey, data)
+ * (store.go:530) and the 128 bkt.Put(k, value) calls of
+ * iterator/cursor_test.go:235 do to an ordered bucket one key at a time, after
+ * which the next Seek sees the key. The stable merge of two sorted columns.
+ * Inputs. A and B are each what honu_sort_keys writes: a sorted column of
+ * 29-byte rows at any byte alignment with the valid keys in [0, v), v =
+ * min(d_valid[0], n), the rows of the invalid keys behind them in index
+ * order, and the matching d_order. d_valid_a and d_valid_b are read on the
+ * device, so the call follows the two sorts, or an earlier merge, on the same
+ * stream with no host round trip. b_base is added to every index taken from
+ * d_order_b: the number of records that precede B's in the caller's
+ * concatenated record arrays, na for a first merge of two sorts, the running
+ * total when chaining.
+ * Outputs, rows and indices [0, na + nb), and d_valid_out[0] = va + vb.
+ * Positions [0, va + vb) hold the stable merge of A's valid rows and B's by
+ * bytes.Compare: on equal keys every A row precedes every B row, and each
+ * side keeps its own order. The tail [va + vb, na + nb) is A's invalid rows
+ * [va, na), then B's [vb, nb), their bytes as they stand, their indices
+ * unchanged for A and + b_base for B. With b_base = na every output equals,
+ * bit for bit, what honu_sort_keys returns for the concatenated key and
+ * status columns (that sort is stable and puts equal keys in ascending
+ * index), so the result is fit for honu_key_seek, honu_key_objects and a
+ * further honu_key_merge.
+ * Put semantics. bbolt's Put of a stored key replaces its value. Here equal
+ * keys stay one run, as they do after honu_sort_keys, and the run's last row
+ * is the latest arrival: what honu_seek.latest, d_order[end - 1], returns.
+ * d_order_out may be NULL: d_order_a and d_order_b are then ignored and only
+ * the column is merged. Given, it needs both input orders.
+ * The write set is exactly d_sorted_out[0, 29 (na + nb)), d_order_out[0, na +
+ * nb) and d_valid_out[0]; the outputs must not overlap the inputs. With na +
+ * nb == 0 only d_valid_out[0] = 0 is written. No workspace and no context
+ * scratch: calls on different streams may share a context. Asynchronous on
+ * `stream`, no host synchronisation, no allocation; replays from a captured
+ * graph.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for na + nb above 2^32 - 1;
+ * HONU_E_ARG for a NULL ctx, d_valid_a, d_valid_b or d_valid_out, a NULL
+ * column or output column with a non-zero count, d_order_out without both
+ * input orders, b_base + nb above 2^32 - 1, or a misaligned pointer (4 bytes:
+ * the orders; 8 bytes: the valid counts).
+ * The get-only param "merge_tile" is the output positions one workgroup
+ * produces. */
+int32_t honu_key_merge(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t *d_order_a,
+                       const uint64_t *d_valid_a, uint64_t na, const uint8_t *d_sorted_b,
+                       const uint32_t *d_order_b, const uint64_t *d_valid_b, uint64_t nb,
+                       uint32_t b_base, uint8_t *d_sorted_out, uint32_t *d_order_out,
+                       uint64_t *d_valid_out, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
