@@ -831,6 +831,66 @@ func (c *Codec) MergeKeys(a, b *KeyOrder) (*KeyOrder, error) {
 	return o, nil
 }
 
+// DeleteKeys is a batch of Deletes from an ordered bucket: the loop "Delete all
+// collection versions" of Store.Drop (store.go:378-383: cursor.Seek(id[:]),
+// then collections.Delete(key) while bytes.HasPrefix(key, id[:])) and the
+// tx.DeleteBucket behind it (store.go:399-404). del is the SortKeys order of
+// the keys to delete, of which only the first probeLen bytes count: 29 a key,
+// 17 an ObjectPrefix, 16 a bare id, 0 everything; nil deletes by no list. With
+// superseded every record that a later record of the same key replaced goes as
+// well (bbolt's Put of a stored key replaces its value; MergeKeys keeps the
+// run), so a key's Seek range is one row again. The loop in store.go deletes
+// while it walks with cursor.Next(), which bbolt documents as able to skip
+// keys; this does what the loop states, every key with the prefix. The result
+// is an order like SortKeys': Valid counts the records that stay, and
+// Order[Valid : Valid+removed] are the records that went, in key order, whose
+// values the caller frees. o and del are not changed and stay the caller's to
+// Free. The result takes SeekKeys, Has, Exists, MergeKeys and a further
+// DeleteKeys.
+//
+// UNCOMPILED, like the rest of this file. honu_key_delete is exercised on the
+// GPU from Python (tests/test_gpu_key_delete.py), graph capture included.
+func (c *Codec) DeleteKeys(o, del *KeyOrder, probeLen int, superseded bool) (out *KeyOrder, removed uint64, err error) {
+	n := o.n
+	out = &KeyOrder{n: n}
+	out.order, out.sorted, out.valid = device(uintptr(4*n)), device(uintptr(C.HONU_KEY_LEN*n)), device(8)
+	workBytes := uint64(C.honu_key_delete_workspace(C.uint64_t(n)))
+	work, dRemoved := device(uintptr(workBytes)), device(8)
+	defer work.free()
+	defer dRemoved.free()
+	hOrder, hCounts := pinned(uintptr(4*n)), pinned(16)
+	defer hOrder.free()
+	defer hCounts.free()
+	var dSorted *C.uint8_t
+	var dValid *C.uint64_t
+	var m C.uint64_t
+	if del != nil && del.n > 0 {
+		dSorted, dValid, m = (*C.uint8_t)(del.sorted.p), (*C.uint64_t)(del.valid.p), C.uint64_t(del.n)
+	}
+	var flags C.uint32_t
+	if superseded {
+		flags = C.HONU_DELETE_SUPERSEDED
+	}
+	for _, s := range []C.int32_t{
+		C.honu_key_delete(c.ctx, (*C.uint8_t)(o.sorted.p), (*C.uint32_t)(o.order.p), (*C.uint64_t)(o.valid.p),
+			C.uint64_t(n), dSorted, dValid, m, C.uint32_t(probeLen), flags, (*C.uint8_t)(out.sorted.p),
+			(*C.uint32_t)(out.order.p), (*C.uint64_t)(out.valid.p), (*C.uint64_t)(dRemoved.p), work.p,
+			C.uint64_t(workBytes), c.stream),
+		C.honu_memcpy_d2h(hOrder.p, out.order.p, C.uint64_t(4*n), c.stream),
+		C.honu_memcpy_d2h(hCounts.p, out.valid.p, 8, c.stream),
+		C.honu_memcpy_d2h(unsafe.Add(hCounts.p, 8), dRemoved.p, 8, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_key_delete", s); err != nil {
+			out.Free()
+			return nil, 0, err
+		}
+	}
+	out.Order = append([]uint32(nil), unsafe.Slice((*uint32)(hOrder.p), n)...)
+	out.Valid = *(*uint64)(hCounts.p)
+	return out, *(*uint64)(unsafe.Add(hCounts.p, 8)), nil
+}
+
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&
 // bytes.HasPrefix(key, probe) of the key Seek lands on.
 func (c *Codec) Has(o *KeyOrder, probes [][]byte) ([]bool, error) {

@@ -56,6 +56,8 @@ _PROTOS = {
     "honu_sizeof_seek": (U64, []),
     "honu_key_seek": (I32, [P, P, P, U64, P, P, C.c_uint32, U64, P, P, P, P]),
     "honu_key_merge": (I32, [P, P, P, P, U64, P, P, P, U64, C.c_uint32, P, P, P, P]),
+    "honu_key_delete_workspace": (U64, [U64]),
+    "honu_key_delete": (I32, [P, P, P, P, U64, P, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P, U64, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -365,6 +365,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "seek_auto_probes")) *value = (int64_t)seek_auto_probes();  // read only: what
     else if (!strcmp(name, "seek_auto_keys")) *value = (int64_t)seek_auto_keys();      // "seek_variant" 0 picks by
     else if (!strcmp(name, "merge_tile")) *value = merge_tile();  // read only: output positions per workgroup of the merge
+    else if (!strcmp(name, "delete_tile")) *value = delete_tile();  // read only: column positions per workgroup of the delete
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -821,6 +822,38 @@ int32_t honu_key_merge(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t 
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_merge(d_sorted_a, d_order_a, d_valid_a, na, d_sorted_b, d_order_b, d_valid_b, nb, b_base,
                             d_sorted_out, d_order_out, d_valid_out, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a batch of Deletes from the sorted column (store.go:378-383, 399-404) and
+// the rows a Put superseded
+// ---------------------------------------------------------------------------
+uint64_t honu_key_delete_workspace(uint64_t n) { return delete_workspace_bytes(n); }
+
+int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_order, const uint64_t *d_valid,
+                        uint64_t n, const uint8_t *d_del, const uint64_t *d_valid_del, uint64_t m,
+                        uint32_t probe_len, uint32_t flags, uint8_t *d_sorted_out, uint32_t *d_order_out,
+                        uint64_t *d_valid_out, uint64_t *d_removed, void *d_work, uint64_t work_bytes,
+                        void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    // the tiles' kept counts are scanned with the context's scan state, which covers max_records rows
+    if (delete_tiles(n) > ctx->max_n) return HONU_E_WORKSPACE;
+    if (probe_len > HONU_KEY_LEN) return arg_fail("probe_len above 29");
+    if (flags & ~(uint32_t)HONU_DELETE_SUPERSEDED) return arg_fail("unknown flag bits");
+    if (!d_valid || !d_valid_out || (m && !d_valid_del)) return arg_fail("null valid count");
+    if ((n && (!d_sorted || !d_sorted_out)) || (m && !d_del)) return arg_fail("null column");
+    if (n && d_order_out && !d_order) return arg_fail("d_order_out needs d_order");
+    if (!aligned(d_order, 4) || !aligned(d_order_out, 4) || !aligned(d_valid, 8) || !aligned(d_valid_del, 8) ||
+        !aligned(d_valid_out, 8) || !aligned(d_removed, 8))
+        return arg_fail("orders 4-byte / counts 8-byte aligned");
+    const uint64_t need = delete_workspace_bytes(n);
+    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_delete_workspace(n)");
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_delete(d_sorted, d_order, d_valid, n, d_del, d_valid_del, m, probe_len, flags, d_sorted_out,
+                             d_order_out, d_valid_out, d_removed, d_work, ctx->scan, (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -275,6 +275,19 @@ hipError_t launch_key_merge(const uint8_t *sa, const uint32_t *oa, const uint64_
                             const uint8_t *sb, const uint32_t *ob, const uint64_t *valid_b, uint64_t nb,
                             uint32_t b_base, uint8_t *out, uint32_t *order, uint64_t *valid_out, hipStream_t s);
 
+// delete.hip: a batch of Deletes (store.go:378-383, 399-404) from the sorted column and the rows
+// a Put superseded: a stable compaction, kept rows, removed rows, the invalid tail. n, m <=
+// 2^32 - 1; order_out == null compacts the column alone; removed may be null. The workspace is
+// the caller's (delete_workspace_bytes(n)). The tiles' counts go through launch_scan: delete_tiles(n)
+// must not exceed the rows the context's scan state covers (its max_records)
+uint32_t delete_tile();
+uint64_t delete_tiles(uint64_t n);
+uint64_t delete_workspace_bytes(uint64_t n);
+hipError_t launch_key_delete(const uint8_t *sorted, const uint32_t *order, const uint64_t *valid, uint64_t n,
+                             const uint8_t *del, const uint64_t *valid_del, uint64_t m, uint32_t probe_len,
+                             uint32_t flags, uint8_t *out, uint32_t *order_out, uint64_t *valid_out,
+                             uint64_t *removed, void *work, const ScanState &S, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -40,27 +40,6 @@ uint32_t seek_fence() { return SEEK_FENCE; }
 uint64_t seek_auto_probes() { return SEEK_AUTO_PROBES; }
 uint64_t seek_auto_keys() { return SEEK_AUTO_KEYS; }
 
-// the packed words' mask of a probe_len-byte prefix: key byte j is packed byte j + 1
-struct SeekMask {
-    uint32_t w[SORT_KEY_WORDS];
-};
-
-static SeekMask seek_mask(uint32_t probe_len) {
-    SeekMask M;
-    for (int i = 0; i < SORT_KEY_WORDS; i++) {
-        M.w[i] = 0;
-        for (int b = 0; b < 4; b++)
-            if ((uint32_t)(4 * i + b) < probe_len + 1) M.w[i] |= 0xFFu << (8 * (3 - b));
-    }
-    return M;
-}
-
-HONU_DEV void load_masked(const uint8_t *k, const SeekMask &M, uint32_t w[SORT_KEY_WORDS]) {
-    pack_key(k, true, w);
-#pragma unroll
-    for (int i = 0; i < SORT_KEY_WORDS; i++) w[i] &= M.w[i];
-}
-
 // bytes.Compare of two packed keys: -1, 0, 1 (word 0 is the most significant)
 HONU_DEV int cmp_packed(const uint32_t k[SORT_KEY_WORDS], const uint32_t p[SORT_KEY_WORDS]) {
     int c = 0;

@@ -12,7 +12,11 @@ statement of Cursor.Seek (iterator/cursor.go:44-55) and Collection.Has
 (collection.go:47-51) over such a sorted list; the batch form is
 Codec.seek_keys (honu_key_seek). merge() is the host statement of a batch of
 Puts into such a list (store.go:232, 395, 530); the batch form is
-Codec.merge_keys (honu_key_merge).
+Codec.merge_keys (honu_key_merge). delete() is the host statement of a batch of
+Deletes from such a list (the loop of Store.Drop, store.go:378-383, and its
+DeleteBucket, store.go:399-404) and compact() of what a Put of a stored key
+does to the row it replaces; the batch form of both is Codec.delete_keys
+(honu_key_delete).
 """
 from __future__ import annotations
 
@@ -151,6 +155,40 @@ def merge(a: Sequence[bytes], b: Sequence[bytes]) -> List[bytes]:
     out.extend(a[i:])
     out.extend(b[j:])
     return out
+
+
+def delete(sorted_keys: Sequence[bytes], probes: Iterable[bytes]):
+    """A batch of Deletes from an ordered bucket: (kept, removed), both in the
+    list's order. A probe is a byte string of any length and removes every key
+    that has it as prefix: a whole key is bucket.Delete(key); an id or an
+    ObjectPrefix is the loop "Delete all collection versions" of Store.Drop
+    (store.go:378-383: cursor.Seek(id[:]), then collections.Delete(key) while
+    bytes.HasPrefix(key, id[:])); the empty probe is the tx.DeleteBucket behind
+    it (store.go:399-404). The Go loop deletes while it walks with
+    cursor.Next(), which bbolt documents as able to skip keys; this is what
+    the loop states, every key with the prefix. A probe that matches nothing
+    is not an error, as bbolt's Delete of an absent key returns nil; probes
+    may repeat. The rows returned are the objects given, not copies. The batch
+    form on the GPU is Codec.delete_keys (honu_key_delete in
+    include/honu_codec.h)."""
+    gone = [False] * len(sorted_keys)
+    for probe in probes:
+        pos, end = seek(sorted_keys, probe)
+        for p in range(pos, end):
+            gone[p] = True
+    return ([k for k, g in zip(sorted_keys, gone) if not g], [k for k, g in zip(sorted_keys, gone) if g])
+
+
+def compact(sorted_keys: Sequence[bytes]):
+    """What a Put of a stored key does to the row it replaces: (kept, removed),
+    both in the list's order, kept the last row of every run of equal keys.
+    bbolt's Put replaces the value; merge() keeps the run, its last row the
+    latest arrival, and this drops the rows before it. The rows returned are
+    the objects given, not copies. The batch form on the GPU is
+    Codec.delete_keys(..., superseded=True) (HONU_DELETE_SUPERSEDED)."""
+    n = len(sorted_keys)
+    gone = [p + 1 < n and bytes(sorted_keys[p + 1]) == bytes(sorted_keys[p]) for p in range(n)]
+    return ([k for k, g in zip(sorted_keys, gone) if not g], [k for k, g in zip(sorted_keys, gone) if g])
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

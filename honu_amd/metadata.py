@@ -64,6 +64,7 @@ SEEK_DTYPE = np.dtype(
 )
 SEEK_NONE = 0xFFFFFFFF
 SEEK_FOUND, SEEK_END, SEEK_EXACT, SEEK_FIRST_LIVE, SEEK_LATEST_LIVE, SEEK_SKIPPED = (1 << b for b in range(6))
+DELETE_SUPERSEDED = 1 << 0  # honu_key_delete flag (Codec.delete_keys): only a run's last row stays
 
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1

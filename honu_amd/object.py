@@ -23,7 +23,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .metadata import (ACL_DTYPE, INFO_DTYPE, META_DTYPE, HostBatch, Metadata, pack_batch,
+from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, INFO_DTYPE, META_DTYPE, HostBatch, Metadata, pack_batch,
                        unpack_row)
 
 StorageVersion = 1  # object.go:14
@@ -358,6 +358,39 @@ class Codec:
         torch = _torch()
         return (out[:29 * (na + nb)], order[:4 * (na + nb)].view(torch.int32) if with_order else None,
                 valid[:8].view(torch.int64))
+
+    def delete_workspace(self, n: int):
+        """The workspace of delete_keys for a column of n rows (honu_key_delete_workspace)."""
+        nbytes = int(self.lib.honu_key_delete_workspace(n))
+        return self._empty(nbytes), nbytes
+
+    def delete_keys(self, sorted_keys, order, valid, del_sorted, del_valid, probe_len: int = 29,
+                    superseded: bool = False):
+        """A batch of Deletes from the sorted column (the loop of Store.Drop,
+        store.go:378-383, and its DeleteBucket, store.go:399-404): every valid
+        row whose first probe_len bytes equal those of a valid row of
+        del_sorted (sort_keys' sorted column and valid count over the keys to
+        delete; None, None for no list) goes, and with `superseded` every row
+        that the next valid row repeats (a Put replaced it). Returns (sorted
+        column, order as an int32 view or None when `order` is None, valid
+        count, removed count, both one int64), on the device: the rows that
+        stay in [0, valid), the rows that went in [valid, valid + removed),
+        then the invalid tail, so it feeds seek_keys, key_objects, merge_keys
+        and a further delete_keys."""
+        n = sorted_keys.numel() // 29
+        m = 0 if del_sorted is None else del_sorted.numel() // 29
+        out = self._empty(29 * n)
+        order_out = self._empty(4 * n) if order is not None else None
+        valid_out, removed = self._empty(8), self._empty(8)
+        work, work_bytes = self.delete_workspace(n)
+        _lib.check(self.lib.honu_key_delete(
+            self.ctx, _lib.ptr(sorted_keys), _lib.ptr(order), _lib.ptr(valid), n, _lib.ptr(del_sorted) if m else 0,
+            _lib.ptr(del_valid) if m else 0, m, probe_len, DELETE_SUPERSEDED if superseded else 0, _lib.ptr(out),
+            _lib.ptr(order_out), _lib.ptr(valid_out), _lib.ptr(removed), _lib.ptr(work), work_bytes, self.stream),
+            "honu_key_delete")
+        torch = _torch()
+        return (out[:29 * n], order_out[:4 * n].view(torch.int32) if order is not None else None,
+                valid_out[:8].view(torch.int64), removed[:8].view(torch.int64))
 
 
 _default: Optional[Codec] = None

@@ -20,6 +20,7 @@
  *   an object's versions        keys/keys.go:73-92     honu_key_objects (ranges of the order, latest)
  *   Cursor.Seek, Has, Exists    iterator/cursor.go:44-55  honu_key_seek (positions of a batch of probes)
  *   bucket.Put (a batch)        store.go:232, 395, 530 honu_key_merge (stable merge into the sorted column)
+ *   bucket.Delete (a batch)     store.go:378-383, 399-404 honu_key_delete (stable compaction of the sorted column)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -690,6 +691,83 @@ int32_t honu_key_merge(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t 
                        const uint32_t *d_order_b, const uint64_t *d_valid_b, uint64_t nb,
                        uint32_t b_base, uint8_t *d_sorted_out, uint32_t *d_order_out,
                        uint64_t *d_valid_out, void *stream);
+
+/* honu_key_delete flags */
+enum { HONU_DELETE_SUPERSEDED = 1u << 0 /* also remove every row that the next valid row repeats */ };
+
+/* Bytes of honu_key_delete's workspace for a column of n rows: a multiple of
+ * 256, monotonic in n, 0 for n == 0; needs no device. */
+uint64_t honu_key_delete_workspace(uint64_t n);
+
+/* A batch of Deletes from the sorted key column: what the loop "Delete all
+ * collection versions" of Store.Drop (store.go:378-383: cursor.Seek(id[:]),
+ * then collections.Delete(key) while bytes.HasPrefix(key, id[:])) and the
+ * tx.DeleteBucket behind it (store.go:399-404) do to an ordered bucket one key
+ * at a time, and what every Put of a stored key does to the row it replaces.
+ * A stable compaction of the column.
+ * Inputs. The column is what honu_sort_keys or honu_key_merge writes: n rows
+ * of 29 bytes at any byte alignment, the valid keys in [0, v), v =
+ * min(d_valid[0], n), and the matching d_order. The delete list is a sorted
+ * column of the same kind, a honu_sort_keys output over the keys to delete: m
+ * rows, of which [0, vd) count, vd = min(d_valid_del[0], m). Both counts are
+ * read on the device, so the call follows the sorts, a merge or an earlier
+ * delete on the same stream with no host round trip. Only the first probe_len
+ * bytes (0..29, one length per call) of a delete row count, as in
+ * honu_key_seek: 29 is bucket.Delete(key), 17 an ObjectPrefix (keys.go:74-79),
+ * 16 the bare id as store.go:379 literally passes it, and 0 with vd >= 1
+ * removes every valid row (the DeleteBucket of store.go:402, a Truncate). A
+ * column sorted over 29 bytes is sorted over every prefix length, so the list
+ * needs no second sort. Delete rows may repeat; one that matches nothing is
+ * not an error, as bbolt's Delete of an absent key returns nil. m == 0 with
+ * d_del and d_valid_del NULL is allowed.
+ * Which rows go. A valid row p < v is removed when (a) its first probe_len
+ * bytes equal those of some delete row in [0, vd), or (b)
+ * HONU_DELETE_SUPERSEDED is set, p + 1 < v and row p + 1 has the same 29
+ * bytes: a later arrival replaced it (the Put semantics of honu_key_merge), so
+ * of a run of equal keys only the last row stays, the one honu_seek.latest
+ * names. Rows of the column at or past v and delete rows at or past vd take
+ * no part, even where their bytes match.
+ * Outputs, n rows and n indices, always a permutation of the input's: [0,
+ * kept) the rows that stay, in column order; [kept, kept + removed) the rows
+ * that go, in column order, whose d_order_out values are the record indices
+ * whose values a caller frees; [v, n) the invalid tail as it stands.
+ * d_valid_out[0] = kept and, where d_removed is given, d_removed[0] = removed
+ * = v - kept, so the result is fit for honu_key_seek, honu_key_objects,
+ * honu_key_merge and a further honu_key_delete. d_order_out may be NULL:
+ * d_order is then ignored and only the column is compacted. Given, it needs
+ * d_order.
+ * As written and as documented. The loop at store.go:379-383 calls
+ * bucket.Delete while it walks with cursor.Next(), which bbolt documents as
+ * able to skip keys. This call does what the loop states ("Delete all
+ * collection versions"): every key with the prefix goes.
+ * The write set is exactly d_sorted_out[0, 29 n), d_order_out[0, n),
+ * d_valid_out[0] and d_removed[0], besides the workspace; the outputs must not
+ * overlap the inputs. With n == 0 only the two counts (0) are written.
+ * d_work is honu_key_delete_workspace(n) bytes, 256-byte aligned (unused,
+ * and NULL allowed, when that is 0). The kept counts of the tiles, one per
+ * "delete_tile" rows, are summed by the context's scan (the one behind
+ * honu_exclusive_scan), whose state covers max_records rows: the column may
+ * have up to "delete_tile" * max_records rows (1024 rows per record the
+ * context was created for), and one context serves one stream at a time, as
+ * for honu_sort_keys. Asynchronous on
+ * `stream`, no host synchronisation, no allocation; replays from a captured
+ * graph, with the counts changed on the device between replays.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for n or m above 2^32 - 1,
+ * or for n above "delete_tile" * max_records (more tiles than the context's
+ * scan covers; honu_sort_keys refuses n above max_records the same way);
+ * HONU_E_ARG for a NULL ctx, d_valid or d_valid_out, a NULL d_valid_del or
+ * d_del with m > 0, a NULL column or output column with n > 0, d_order_out
+ * without d_order with n > 0, probe_len > 29, unknown flag bits, work_bytes
+ * below honu_key_delete_workspace(n), a NULL or misaligned (256) workspace
+ * when that size is not 0, or a misaligned pointer (4 bytes: the orders; 8
+ * bytes: the counts).
+ * The get-only param "delete_tile" is the column positions one workgroup
+ * takes. */
+int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_order,
+                        const uint64_t *d_valid, uint64_t n, const uint8_t *d_del,
+                        const uint64_t *d_valid_del, uint64_t m, uint32_t probe_len, uint32_t flags,
+                        uint8_t *d_sorted_out, uint32_t *d_order_out, uint64_t *d_valid_out,
+                        uint64_t *d_removed, void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
