@@ -866,6 +866,7 @@ int32_t honu_system_sizes(honu_ctx *ctx, const honu_collection *d_rows, uint64_t
                           uint64_t n, uint64_t *d_sizes, int32_t *d_status, void *stream) {
     if (!ctx) return arg_fail("ctx");
     if (n && (!d_rows || !d_sizes)) return arg_fail("null pointer");
+    if (!aligned(d_rows, 16)) return arg_fail("rows must be 16-byte aligned");
     if (!aligned(d_acl, 4) || !aligned(d_regions, 4) || !aligned(d_index, 8))
         return arg_fail("tables must be aligned");
     HIPCHK(hipSetDevice(ctx->device));
@@ -881,6 +882,8 @@ int32_t honu_system_encode(honu_ctx *ctx, const honu_collection *d_rows, const u
                            void *stream) {
     if (!ctx) return arg_fail("ctx");
     if (n && (!d_rows || !d_out || !d_out_off || !d_status)) return arg_fail("null pointer");
+    if (!aligned(d_rows, 16) || !aligned(d_out, 16))
+        return arg_fail("rows and output arena must be 16-byte aligned");
     if (!aligned(d_acl, 4) || !aligned(d_regions, 4) || !aligned(d_index, 8))
         return arg_fail("tables must be aligned");
     HIPCHK(hipSetDevice(ctx->device));
@@ -896,6 +899,13 @@ int32_t honu_system_marshal_batch(honu_ctx *ctx, const honu_collection *d_rows,
                                   uint64_t index_len, uint64_t n, uint8_t *d_out,
                                   uint64_t out_cap, uint64_t *d_out_off, int32_t *d_status,
                                   void *stream) {
+    // the checks of the phases below, before the first of them launches: a
+    // refused call has stored nothing
+    if (!ctx) return arg_fail("ctx");
+    if (n > ctx->max_n) return HONU_E_WORKSPACE;
+    if (n && (!d_rows || !d_out || !d_out_off || !d_status)) return arg_fail("null pointer");
+    if (!aligned(d_rows, 16) || !aligned(d_out, 16))
+        return arg_fail("rows and output arena must be 16-byte aligned");
     int32_t st = honu_system_sizes(ctx, d_rows, var_len, d_acl, acl_len, d_regions, regions_len,
                                    d_index, index_len, n, d_out_off, d_status, stream);
     if (st) return st;
@@ -913,6 +923,7 @@ static int32_t collection_decode(honu_ctx *ctx, bool headless, const uint8_t *d_
     if (!ctx) return arg_fail("ctx");
     if (n > ctx->max_n) return HONU_E_WORKSPACE;
     if (n && (!d_rec || !d_rec_off || !d_rows || !d_status)) return arg_fail("null pointer");
+    if (!aligned(d_rec, 16)) return arg_fail("records arena must be 16-byte aligned");
     if (!aligned(d_rows, 16) || !aligned(d_acl, 4) || !aligned(d_regions, 4) ||
         !aligned(d_index, 8))
         return arg_fail("rows 16-byte / tables 4- and 8-byte aligned");

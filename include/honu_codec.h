@@ -347,6 +347,8 @@ const char *honu_last_error(void);
  * encoded gets size 0 and d_status[i] = HONU_ERR_PANIC when HONU_HAS_META is
  * clear (Marshal(nil, …) dereferences nil, metadata.go:66) or HONU_ERR_INPUT
  * when a span or list lies outside its arena; otherwise d_status[i] = HONU_OK.
+ * A span is validated only when its struct's presence bit is set, as Go never
+ * reads a nil struct's fields; mime is always live.
  * Arguments as for honu_encode. */
 int32_t honu_encode_sizes(honu_ctx *ctx, const honu_meta *d_meta, uint64_t var_len,
                           const honu_acl *d_acl, uint64_t acl_len, const uint32_t *d_regions,
@@ -779,7 +781,7 @@ int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *
  * non-nil WriteRegions). */
 #define HONU_HAS_COLLECTION HONU_HAS_META
 
-/* One metadata.Collection (collection.go:16-33) as a fixed 352-byte row.
+/* One metadata.Collection (collection.go:16-33) as a fixed 368-byte row.
  * Field meanings, spans, list descriptors and time encoding as honu_meta;
  * index_off/index_count describe Collection.Indexes in a honu_index table. */
 typedef struct honu_collection {
@@ -853,20 +855,29 @@ typedef struct honu_index {
 /* object.MarshalSystem(collection) (system.go:10-31) for n collections:
  * 0x01 | EncodeStruct(collection) | 0x00. Exact encoded lengths in d_sizes,
  * statuses as honu_encode_sizes (HONU_ERR_INPUT for spans or lists outside
- * their arenas). A row without HONU_HAS_COLLECTION encodes MarshalSystem(nil)
- * = 01 00 00. */
+ * their arenas). A span is validated only when its struct's presence bit is
+ * set, as Go never reads a nil struct's fields; name is always live. A row
+ * without HONU_HAS_COLLECTION encodes MarshalSystem(nil) = 01 00 00. d_rows
+ * must be 16-byte aligned, d_acl and d_regions 4-byte, d_index 8-byte;
+ * d_status may be NULL. */
 int32_t honu_system_sizes(honu_ctx *ctx, const honu_collection *d_rows, uint64_t var_len,
                           const honu_acl *d_acl, uint64_t acl_len, const uint32_t *d_regions,
                           uint64_t regions_len, const honu_index *d_index, uint64_t index_len,
                           uint64_t n, uint64_t *d_sizes, int32_t *d_status, void *stream);
 /* Writes records at d_out + d_out_off[i] (offsets from honu_exclusive_scan of
- * the sizes); skips records whose status is not HONU_OK. */
+ * the sizes); skips records whose status is not HONU_OK, and gives those
+ * whose range ends past out_cap HONU_ERR_CAPACITY (nothing of them is
+ * stored; the call still returns HONU_OK). d_rows and d_out must be 16-byte
+ * aligned, the tables as for honu_system_sizes. */
 int32_t honu_system_encode(honu_ctx *ctx, const honu_collection *d_rows, const uint8_t *d_var,
                            const honu_acl *d_acl, const uint32_t *d_regions,
                            const honu_index *d_index, uint64_t n, uint8_t *d_out,
                            uint64_t out_cap, const uint64_t *d_out_off, int32_t *d_status,
                            void *stream);
-/* sizes + scan (d_out_off has n+1 entries) + encode. */
+/* sizes + scan (d_out_off has n+1 entries) + encode. Every argument check of
+ * the three (alignments, null pointers, n against max_records:
+ * HONU_E_WORKSPACE) is made before the first launch: a refused call has
+ * stored nothing. */
 int32_t honu_system_marshal_batch(honu_ctx *ctx, const honu_collection *d_rows,
                                   const uint8_t *d_var, uint64_t var_len, const honu_acl *d_acl,
                                   uint64_t acl_len, const uint32_t *d_regions,
@@ -881,8 +892,16 @@ int32_t honu_system_marshal_batch(honu_ctx *ctx, const honu_collection *d_rows,
  * collection leaves a zero row). ACL entries, regions and index rows go to
  * the tables (capacities in entries); d_status[i] is the UnmarshalSystem
  * error, HONU_ERR_PANIC for records shorter than 2 bytes (slice bounds) and
- * for counts Go's make() rejects. d_totals (3 u64, device): ACL entries,
- * regions, indexes. */
+ * for counts Go's make() rejects. d_totals (3 u64, device, optional): the
+ * ACL entries, regions and indexes the batch needs, whatever the capacities.
+ * A record whose lists do not fit a table keeps its row, with the offsets its
+ * lists would have had, gets HONU_ERR_CAPACITY in d_status, and none of its
+ * entries is stored; the call returns HONU_OK, as honu_decode_batch does (a
+ * capacity shows in the statuses and in the totals, never in the return
+ * code). d_rec and d_rows must be 16-byte aligned (the decoder loads whole
+ * aligned 16-byte blocks relative to d_rec), d_acl and d_regions 4-byte,
+ * d_index 8-byte; a table may be NULL only with capacity 0. n above
+ * max_records: HONU_E_WORKSPACE. A refused call has stored nothing. */
 int32_t honu_system_decode_batch(honu_ctx *ctx, const uint8_t *d_rec, const uint64_t *d_rec_off,
                                  uint64_t n, honu_collection *d_rows, int32_t *d_status,
                                  honu_acl *d_acl, uint64_t acl_cap, uint32_t *d_regions,

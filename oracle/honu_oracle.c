@@ -165,15 +165,19 @@ static const uint8_t *span_ptr(const uint8_t *var, uint64_t var_len, honu_span s
 static int encode_meta(owriter *w, const honu_meta *m, const uint8_t *var, uint64_t var_len,
                        const honu_acl *acl, uint64_t acl_len, const uint32_t *regions,
                        uint64_t regions_len) {
-    int bad = 0;
-    const uint8_t *name = span_ptr(var, var_len, m->schema_name, &bad);
+    /* Go never reads a nil struct's fields: a span is validated only when its
+     * struct's presence bit is set (mime is always live) */
+    int bad = 0, dead = 0;
+    const uint32_t pr = m->present;
+    const uint8_t *name = span_ptr(var, var_len, m->schema_name, pr & HONU_HAS_SCHEMA ? &bad : &dead);
     const uint8_t *mime = span_ptr(var, var_len, m->mime, &bad);
-    const uint8_t *ip = span_ptr(var, var_len, m->ip_address, &bad);
-    const uint8_t *ua = span_ptr(var, var_len, m->user_agent, &bad);
-    const uint8_t *pk = span_ptr(var, var_len, m->public_key_id, &bad);
-    const uint8_t *ek = span_ptr(var, var_len, m->encryption_key, &bad);
-    const uint8_t *hs = span_ptr(var, var_len, m->hmac_secret, &bad);
-    const uint8_t *sg = span_ptr(var, var_len, m->signature, &bad);
+    int *pub = pr & HONU_HAS_PUBLISHER ? &bad : &dead, *enc = pr & HONU_HAS_ENCRYPTION ? &bad : &dead;
+    const uint8_t *ip = span_ptr(var, var_len, m->ip_address, pub);
+    const uint8_t *ua = span_ptr(var, var_len, m->user_agent, pub);
+    const uint8_t *pk = span_ptr(var, var_len, m->public_key_id, enc);
+    const uint8_t *ek = span_ptr(var, var_len, m->encryption_key, enc);
+    const uint8_t *hs = span_ptr(var, var_len, m->hmac_secret, enc);
+    const uint8_t *sg = span_ptr(var, var_len, m->signature, enc);
     if (m->acl_count && (m->acl_off > acl_len || m->acl_count > acl_len - m->acl_off)) bad = 1;
     if (m->regions_count &&
         (m->regions_off > regions_len || m->regions_count > regions_len - m->regions_off))
@@ -751,15 +755,18 @@ static int encode_collection(owriter *w, const honu_collection *c, const uint8_t
                              uint64_t var_len, const honu_acl *acl, uint64_t acl_len,
                              const uint32_t *regions, uint64_t regions_len, const honu_index *idx,
                              uint64_t idx_len) {
-    int bad = 0;
+    /* as encode_meta: a nil struct's spans are never read (name is always live) */
+    int bad = 0, dead = 0;
+    const uint32_t pr = c->present;
     const uint8_t *name = span_ptr(var, var_len, c->name, &bad);
-    const uint8_t *sname = span_ptr(var, var_len, c->schema_name, &bad);
-    const uint8_t *ip = span_ptr(var, var_len, c->ip_address, &bad);
-    const uint8_t *ua = span_ptr(var, var_len, c->user_agent, &bad);
-    const uint8_t *pk = span_ptr(var, var_len, c->public_key_id, &bad);
-    const uint8_t *ek = span_ptr(var, var_len, c->encryption_key, &bad);
-    const uint8_t *hs = span_ptr(var, var_len, c->hmac_secret, &bad);
-    const uint8_t *sg = span_ptr(var, var_len, c->signature, &bad);
+    const uint8_t *sname = span_ptr(var, var_len, c->schema_name, pr & HONU_HAS_SCHEMA ? &bad : &dead);
+    int *pub = pr & HONU_HAS_PUBLISHER ? &bad : &dead, *enc = pr & HONU_HAS_ENCRYPTION ? &bad : &dead;
+    const uint8_t *ip = span_ptr(var, var_len, c->ip_address, pub);
+    const uint8_t *ua = span_ptr(var, var_len, c->user_agent, pub);
+    const uint8_t *pk = span_ptr(var, var_len, c->public_key_id, enc);
+    const uint8_t *ek = span_ptr(var, var_len, c->encryption_key, enc);
+    const uint8_t *hs = span_ptr(var, var_len, c->hmac_secret, enc);
+    const uint8_t *sg = span_ptr(var, var_len, c->signature, enc);
     if (c->acl_count && (c->acl_off > acl_len || c->acl_count > acl_len - c->acl_off)) bad = 1;
     if (c->regions_count &&
         (c->regions_off > regions_len || c->regions_count > regions_len - c->regions_off))

@@ -233,8 +233,12 @@ def key(row, meta_status: int):
     return st, bytes(out)
 
 
-def system_marshal_batch(sb):
-    """MarshalSystem over a honu_amd.system.SystemHostBatch -> (out, off, status)."""
+def system_marshal_batch(sb, out_cap=None):
+    """MarshalSystem over a honu_amd.system.SystemHostBatch -> (out, off, status).
+
+    out_cap (None: the batch's own total): as marshal_batch's: records ending
+    past it get HONU_ERR_CAPACITY, and the arena comes back untrimmed (the
+    batch's total bytes, POISON where nothing was stored)."""
     lib = load()
     n = len(sb.rows)
     out_off = np.zeros(n + 1, np.uint64)
@@ -243,14 +247,27 @@ def system_marshal_batch(sb):
             len(sb.regions), _p(sb.index), len(sb.index), n)
     lib.oracle_system_marshal_batch(*args, None, 0, _p(out_off), _p(status))
     total = int(out_off[n])
-    out = np.zeros(max(total, 1), np.uint8)
-    lib.oracle_system_marshal_batch(*args, _p(out), total, _p(out_off), _p(status))
-    return out[:total], out_off, status
+    if out_cap is None:
+        out = np.zeros(max(total, 1), np.uint8)
+    else:
+        out = np.full(max(total, int(out_cap), 1), POISON, np.uint8)
+    lib.oracle_system_marshal_batch(*args, _p(out), total if out_cap is None else int(out_cap),
+                                    _p(out_off), _p(status))
+    return (out[:total] if out_cap is None else out), out_off, status
 
 
-def system_decode_batch(rec: np.ndarray, rec_off: np.ndarray, headless: bool = False):
+def system_decode_batch(rec: np.ndarray, rec_off: np.ndarray, headless: bool = False,
+                        acl_cap=None, regions_cap=None, index_cap=None):
     """UnmarshalSystem(obj, &Collection{}) -> (rows, status, acl, regions, index, totals);
-    headless: lani.Unmarshal(obj, &Collection{}) instead (store.go:367)."""
+    headless: lani.Unmarshal(obj, &Collection{}) instead (store.go:367).
+
+    acl_cap, regions_cap, index_cap (table entries): as decode_batch's: the
+    capacities handed to the oracle instead of tables no batch can fill; a
+    record whose lists do not fit keeps its row and gets HONU_ERR_CAPACITY,
+    totals still report what the batch needs. With any of them given the
+    tables come back untrimmed (each longer than its capacity and than the
+    batch needs, POISON where nothing was stored; only the entries of the
+    records with status 0 are specified)."""
     from honu_amd.metadata import ACL_DTYPE
     from honu_amd.system import COLLECTION_DTYPE, INDEX_DTYPE
     lib = load()
@@ -262,13 +279,24 @@ def system_decode_batch(rec: np.ndarray, rec_off: np.ndarray, headless: bool = F
     nbytes = int(rec_off[-1]) if n >= 0 else 0
     rows = np.zeros(max(n, 1), COLLECTION_DTYPE)
     status = np.zeros(max(n, 1), np.int32)
-    acl = np.zeros(nbytes + 1, ACL_DTYPE)
-    reg = np.zeros(nbytes + 1, np.uint32)
-    idx = np.zeros(nbytes + 1, INDEX_DTYPE)
+    capped = not (acl_cap is None and regions_cap is None and index_cap is None)
+
+    def buf(cap, dtype):  # every entry takes >= 1 byte of its record
+        if not capped:
+            return np.zeros(nbytes + 1, dtype)
+        a = np.empty(max(nbytes + 1, int(cap or 0) + 1), dtype)
+        a.view(np.uint8)[:] = POISON
+        return a
+
+    acl, reg, idx = buf(acl_cap, ACL_DTYPE), buf(regions_cap, np.uint32), buf(index_cap, INDEX_DTYPE)
     totals = np.zeros(3, np.uint64)
     fn = lib.oracle_collection_decode_batch if headless else lib.oracle_system_decode_batch
-    fn(_p(rec), _p(rec_off), n, _p(rows), _p(status), _p(acl), len(acl), _p(reg), len(reg),
-       _p(idx), len(idx), _p(totals))
+    fn(_p(rec), _p(rec_off), n, _p(rows), _p(status), _p(acl),
+       len(acl) if acl_cap is None else int(acl_cap), _p(reg),
+       len(reg) if regions_cap is None else int(regions_cap), _p(idx),
+       len(idx) if index_cap is None else int(index_cap), _p(totals))
+    if capped:
+        return rows[:n], status[:n], acl, reg, idx, totals
     return (rows[:n], status[:n], acl[: int(totals[0])], reg[: int(totals[1])],
             idx[: int(totals[2])], totals)
 

@@ -208,3 +208,103 @@ def check_decode(o, oracle_out):
         dr = data_ranges(oinfo)
         _same("data arena", got(o.data), odata, dr)
         guards.assert_untouched(o.data, dr)
+
+
+# --------------------------------------------------------------------------
+# system objects
+# --------------------------------------------------------------------------
+class SysIn:
+    """A SystemHostBatch on the device, each arena at its own phase."""
+
+    def __init__(self, sb, dev, var=0, lists=4, index=8, rows=0):
+        self.n = len(sb.rows)
+        self.t = dict(rows=placed(sb.rows, dev, rows), var=placed(sb.var, dev, var), acl=placed(sb.acl, dev, lists),
+                      reg=placed(sb.regions, dev, lists), idx=placed(sb.index, dev, index))
+        self.rows, self.var, self.acl, self.reg, self.idx = (ptr(self.t[k]) for k in ("rows", "var", "acl", "reg", "idx"))
+        self.var_len, self.acl_len, self.reg_len, self.idx_len = len(sb.var), len(sb.acl), len(sb.regions), len(sb.index)
+
+
+def system_sizes(c, x, sizes, status):
+    """honu_system_sizes; sizes / status: guarded views or device addresses."""
+    a = lambda t: t if isinstance(t, int) else ptr(t)  # noqa: E731
+    return c.lib.honu_system_sizes(c.ctx, x.rows, x.var_len, x.acl, x.acl_len, x.reg, x.reg_len, x.idx, x.idx_len,
+                                   x.n, a(sizes), a(status), c.stream)
+
+
+def system_encode(c, route, x, out, out_cap, out_off, status):
+    """One MarshalSystem of the batch by `route`: "calls" (sizes, the scan in
+    place, encode) or "marshal" (honu_system_marshal_batch). Returns the
+    calls' return codes."""
+    po, pf, ps = ptr(out), ptr(out_off), ptr(status)
+    lib = c.lib
+    if route == "marshal":
+        return [lib.honu_system_marshal_batch(c.ctx, x.rows, x.var, x.var_len, x.acl, x.acl_len, x.reg, x.reg_len,
+                                              x.idx, x.idx_len, x.n, po, out_cap, pf, ps, c.stream)]
+    assert route == "calls"
+    return [system_sizes(c, x, out_off, status), lib.honu_exclusive_scan(c.ctx, pf, x.n, pf, c.stream),
+            lib.honu_system_encode(c.ctx, x.rows, x.var, x.acl, x.reg, x.idx, x.n, po, out_cap, pf, ps, c.stream)]
+
+
+class SysOut:
+    """Guarded outputs of one system decode: rows, statuses, totals and the
+    three tables, allocated at exactly `tot` entries (the oracle's totals)."""
+
+    def __init__(self, n, tot, dev, fill, rows=0, lists=4, index=8):
+        self.n, self.need = n, [int(v) for v in tot]
+        self.rows, self.status = out_buf(368 * n, dev, fill, rows), out_buf(4 * n, dev, fill)
+        self.tot = out_buf(24, dev, fill)
+        self.acl, self.reg = out_buf(20 * self.need[0], dev, fill, lists), out_buf(4 * self.need[1], dev, fill, lists)
+        self.idx = out_buf(112 * self.need[2], dev, fill, index)
+
+    def all(self):
+        return (self.rows, self.status, self.tot, self.acl, self.reg, self.idx)
+
+
+def system_decode(c, headless, d_rec, d_off, o, acl_cap=None, regions_cap=None, index_cap=None, totals=True):
+    """honu_system_decode_batch / honu_collection_decode_batch into `o`; a
+    capacity of 0 passes a NULL table."""
+    caps = [need if cap is None else cap for need, cap in zip(o.need, (acl_cap, regions_cap, index_cap))]
+    tabs = [ptr(t) if cap else 0 for t, cap in zip((o.acl, o.reg, o.idx), caps)]
+    fn = c.lib.honu_collection_decode_batch if headless else c.lib.honu_system_decode_batch
+    return fn(c.ctx, d_rec, d_off, o.n, ptr(o.rows), ptr(o.status), tabs[0], caps[0], tabs[1], caps[1], tabs[2],
+              caps[2], ptr(o.tot) if totals else 0, c.stream)
+
+
+def system_table_ranges(orows, ost):
+    """The byte ranges of the three tables that the rows with status 0 own."""
+    acl, reg, idx = [], [], []
+    for i in np.flatnonzero(ost == 0):
+        r = orows[i]
+        for out, f, size in ((acl, "acl", 20), (reg, "regions", 4), (idx, "index", 112)):
+            o, k = int(r[f + "_off"]), int(r[f + "_count"])
+            if k:
+                out.append((size * o, size * (o + k)))
+    return acl, reg, idx
+
+
+def check_system_decode(o, oracle_out, totals=True):
+    """After a system decode: rows, statuses and totals are the oracle's byte
+    for byte, the table entries of the rows with status 0 too, and nothing
+    else was stored anywhere."""
+    orows, ost, oacl, oreg, oidx, otot = oracle_out
+    n = o.n
+    if totals:
+        assert np.array_equal(got(o.tot, np.uint64), otot)
+    st = got(o.status, np.int32)
+    assert np.array_equal(st, ost), [(int(i), int(st[i]), int(ost[i])) for i in np.flatnonzero(st != ost)[:8]]
+    rows = got(o.rows).reshape(n, 368)
+    want = np.ascontiguousarray(orows).view(np.uint8).reshape(n, 368)
+    bad = np.flatnonzero((rows != want).any(axis=1))
+    assert not len(bad), (bad[:5], np.flatnonzero(rows[bad[0]] != want[bad[0]]))
+    ranges = system_table_ranges(orows, ost)
+    for name, t, ot, r in zip(("ACL", "region", "index"), (o.acl, o.reg, o.idx), (oacl, oreg, oidx), ranges):
+        assert all(b <= block_len(t) for _, b in r), name
+        _same(name + " table", got(t), np.ascontiguousarray(ot).view(np.uint8).reshape(-1), r)
+        guards.assert_untouched(t, r)
+    guards.assert_untouched(o.rows, [(0, 368 * n)])
+    guards.assert_untouched(o.status, [(0, 4 * n)])
+    guards.assert_untouched(o.tot, [(0, 24)] if totals else [])
+
+
+def block_len(t) -> int:
+    return guards.block_of(t).nbytes
