@@ -891,6 +891,113 @@ func (c *Codec) DeleteKeys(o, del *KeyOrder, probeLen int, superseded bool) (out
 	return out, *(*uint64)(unsafe.Add(hCounts.p, 8)), nil
 }
 
+// ListRow is one row of ListKeys: honu_list_row (include/honu_codec.h).
+type ListRow struct {
+	Range  uint32 // which of the seeks it came from
+	Pos    uint32 // position in the sorted order
+	Record uint32 // o.Order[Pos]
+	Flags  uint32 // C.HONU_LIST_ROW_*
+}
+
+func (r ListRow) Head() bool      { return r.Flags&C.HONU_LIST_ROW_HEAD != 0 }
+func (r ListRow) Tombstone() bool { return r.Flags&C.HONU_LIST_ROW_TOMBSTONE != 0 }
+
+// ListKeys is what follows the Seek on every read path, the walk with
+// Cursor.Next() or Cursor.Prev() (iterator/cursor.go:57-89), for a batch of
+// ranges: Collection.List (collection.go:32-35), Versions ("from the most
+// recent version to the oldest", collection.go:106-110), Retrieve ("the latest
+// version", collection.go:97-104) and the loop of store.go:379. seeks are
+// SeekKeys' rows; for each, the rows a cursor over [Pos, End) visits, the
+// ranges in order: forward from Pos, or with reverse from End-1 down; limit
+// (not 0) stops each walk after that many rows, so reverse with limit 1 is the
+// latest version of each range. With latest only the last row of every object
+// (the keys that share an ObjectPrefix, keys.go:74-79) is visited. offsets[q]
+// is where range q's rows start in rows and offsets[len(seeks)] their number.
+// info (the decode's record info rows on the device, or a zero devBuf) sets
+// Tombstone; tombstones are flagged, not filtered (collection.go:132-134), and
+// the record values are not gathered. The first call counts, the second emits:
+// the total is the one host round trip.
+//
+// UNCOMPILED, like the rest of this file. honu_key_list is exercised on the
+// GPU from Python (tests/test_gpu_key_list.py), graph capture included.
+func (c *Codec) ListKeys(o *KeyOrder, seeks []Seek, limit uint32, reverse, latest bool, info devBuf) (rows []ListRow, offsets []uint64, err error) {
+	m := uint64(len(seeks))
+	n := o.n
+	seekSize, rowSize := uint64(C.honu_sizeof_seek()), uint64(C.honu_sizeof_list_row())
+	hSeek, hOff := pinned(uintptr(seekSize*m)), pinned(uintptr(8*(m+1)))
+	defer hSeek.free()
+	defer hOff.free()
+	in := unsafe.Slice((*C.honu_seek)(hSeek.p), m)
+	for q, s := range seeks {
+		in[q].pos, in[q].end, in[q].first = C.uint32_t(s.Pos), C.uint32_t(s.End), C.uint32_t(s.First)
+		in[q].latest, in[q].flags = C.uint32_t(s.Latest), C.uint32_t(s.Flags)
+	}
+	dSeek, dOff, dTotal := device(hSeek.n), device(hOff.n), device(8)
+	defer dSeek.free()
+	defer dOff.free()
+	defer dTotal.free()
+	var flags C.uint32_t
+	if reverse {
+		flags |= C.HONU_LIST_REVERSE
+	}
+	var dObjOff, dLatest, dObjects, work devBuf
+	if latest {
+		if o.keys.p == nil { // MergeKeys and DeleteKeys return no key column in record order
+			return nil, nil, fmt.Errorf("latest needs an order that SortKeys returned")
+		}
+		flags |= C.HONU_LIST_LATEST
+		workBytes := uint64(C.honu_sort_keys_workspace(C.uint64_t(n)))
+		dObjOff, dLatest, dObjects, work = device(uintptr(8*(n+1))), device(uintptr(4*n)), device(8), device(uintptr(workBytes))
+		defer dObjOff.free()
+		defer dLatest.free()
+		defer dObjects.free()
+		defer work.free()
+		if err = call("honu_key_objects", C.honu_key_objects(c.ctx, (*C.uint8_t)(o.keys.p), (*C.uint32_t)(o.order.p),
+			(*C.uint64_t)(o.valid.p), C.uint64_t(n), (*C.uint64_t)(dObjOff.p), (*C.uint32_t)(dLatest.p),
+			(*C.uint64_t)(dObjects.p), work.p, C.uint64_t(workBytes), c.stream)); err != nil {
+			return nil, nil, err
+		}
+	}
+	list := func(dRows devBuf, cap uint64) C.int32_t {
+		return C.honu_key_list(c.ctx, (*C.uint8_t)(o.sorted.p), (*C.uint32_t)(o.order.p), (*C.uint64_t)(o.valid.p),
+			C.uint64_t(n), (*C.honu_seek)(dSeek.p), C.uint64_t(m), C.uint32_t(limit), flags,
+			(*C.uint64_t)(dObjOff.p), (*C.uint64_t)(dObjects.p), (*C.honu_record_info)(info.p),
+			(*C.uint64_t)(dOff.p), (*C.honu_list_row)(dRows.p), nil, C.uint64_t(cap), (*C.uint64_t)(dTotal.p), c.stream)
+	}
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(dSeek.p, hSeek.p, C.uint64_t(hSeek.n), c.stream),
+		list(devBuf{}, 0), // counts only
+		C.honu_memcpy_d2h(hOff.p, dOff.p, C.uint64_t(hOff.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_list", s); err != nil {
+			return nil, nil, err
+		}
+	}
+	offsets = append([]uint64(nil), unsafe.Slice((*uint64)(hOff.p), m+1)...)
+	total := offsets[m]
+	if total == 0 {
+		return nil, offsets, nil
+	}
+	hRows, dRows := pinned(uintptr(rowSize*total)), device(uintptr(rowSize*total))
+	defer hRows.free()
+	defer dRows.free()
+	for _, s := range []C.int32_t{
+		list(dRows, total),
+		C.honu_memcpy_d2h(hRows.p, dRows.p, C.uint64_t(hRows.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_list", s); err != nil {
+			return nil, nil, err
+		}
+	}
+	rows = make([]ListRow, total)
+	for g, r := range unsafe.Slice((*C.honu_list_row)(hRows.p), total) {
+		rows[g] = ListRow{uint32(r._range), uint32(r.pos), uint32(r.record), uint32(r.flags)}
+	}
+	return rows, offsets, nil
+}
+
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&
 // bytes.HasPrefix(key, probe) of the key Seek lands on.
 func (c *Codec) Has(o *KeyOrder, probes [][]byte) ([]bool, error) {

@@ -170,6 +170,7 @@ uint64_t honu_sizeof_collection(void) { return sizeof(honu_collection); }
 uint64_t honu_sizeof_index(void) { return sizeof(honu_index); }
 uint64_t honu_sizeof_record_info(void) { return sizeof(honu_record_info); }
 uint64_t honu_sizeof_seek(void) { return sizeof(honu_seek); }
+uint64_t honu_sizeof_list_row(void) { return sizeof(honu_list_row); }
 const char *honu_last_error(void) { return g_last_error; }
 
 const char *honu_status_string(int32_t st) {
@@ -366,6 +367,8 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "seek_auto_keys")) *value = (int64_t)seek_auto_keys();      // "seek_variant" 0 picks by
     else if (!strcmp(name, "merge_tile")) *value = merge_tile();  // read only: output positions per workgroup of the merge
     else if (!strcmp(name, "delete_tile")) *value = delete_tile();  // read only: column positions per workgroup of the delete
+    else if (!strcmp(name, "list_tile")) *value = list_tile();    // read only: output rows per workgroup of the list
+    else if (!strcmp(name, "list_stage")) *value = list_stage();  // read only: range offsets a workgroup of the list stages in LDS
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -854,6 +857,35 @@ int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_delete(d_sorted, d_order, d_valid, n, d_del, d_valid_del, m, probe_len, flags, d_sorted_out,
                              d_order_out, d_valid_out, d_removed, d_work, ctx->scan, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a batch of cursor walks over seek ranges (iterator/cursor.go:57-89;
+// collection.go:32-35, 97-110; store.go:379)
+// ---------------------------------------------------------------------------
+int32_t honu_key_list(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_order, const uint64_t *d_valid,
+                      uint64_t n, const honu_seek *d_ranges, uint64_t m, uint32_t limit, uint32_t flags,
+                      const uint64_t *d_obj_off, const uint64_t *d_objects, const honu_record_info *d_info,
+                      uint64_t *d_range_off, honu_list_row *d_rows, uint8_t *d_keys_out, uint64_t cap,
+                      uint64_t *d_total, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || cap > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    // the m + 1 counts are scanned in place with the context's scan state, which covers max_records rows
+    if (m + 1 > ctx->max_n) return HONU_E_WORKSPACE;
+    if (flags & ~(uint32_t)(HONU_LIST_REVERSE | HONU_LIST_LATEST)) return arg_fail("unknown flag bits");
+    if (!d_valid || !d_range_off || !d_total) return arg_fail("null d_valid, d_range_off or d_total");
+    if ((m && !d_ranges) || (n && !d_sorted) || (cap && !d_rows)) return arg_fail("null ranges, column or rows");
+    if ((flags & HONU_LIST_LATEST) && (!d_obj_off || !d_objects)) return arg_fail("LATEST needs d_obj_off and d_objects");
+    if (d_info && !d_order) return arg_fail("d_info needs d_order");
+    if (!aligned(d_ranges, 4) || !aligned(d_order, 4) || !aligned(d_valid, 8) || !aligned(d_objects, 8) ||
+        !aligned(d_obj_off, 8) || !aligned(d_range_off, 8) || !aligned(d_total, 8) || !aligned(d_info, 8) ||
+        !aligned(d_rows, 16))
+        return arg_fail("ranges and order 4-byte / counts, offsets and info 8-byte / rows 16-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_list(ctx->geom.num_cu, d_sorted, d_order, d_valid, n, d_ranges, m, limit, flags, d_obj_off,
+                           d_objects, d_info, d_range_off, d_rows, d_keys_out, cap, d_total, ctx->scan,
+                           (hipStream_t)stream));
     return HONU_OK;
 }
 

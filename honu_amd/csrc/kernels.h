@@ -288,6 +288,18 @@ hipError_t launch_key_delete(const uint8_t *sorted, const uint32_t *order, const
                              uint32_t flags, uint8_t *out, uint32_t *order_out, uint64_t *valid_out,
                              uint64_t *removed, void *work, const ScanState &S, hipStream_t s);
 
+// list.hip: a batch of cursor walks (Next / Prev, iterator/cursor.go:57-89) over ranges of the sorted
+// column, honu_key_seek's rows: the rows each would visit, packed, the ranges in order. n, m, cap <=
+// 2^32 - 1. No workspace; the counts are scanned in place in range_off (m + 1 values) through
+// launch_scan: m + 1 must not exceed the rows the context's scan state covers (its max_records)
+uint32_t list_tile();
+uint32_t list_stage();
+hipError_t launch_key_list(int num_cu, const uint8_t *sorted, const uint32_t *order, const uint64_t *valid, uint64_t n,
+                           const honu_seek *ranges, uint64_t m, uint32_t limit, uint32_t flags,
+                           const uint64_t *obj_off, const uint64_t *objects, const honu_record_info *info,
+                           uint64_t *range_off, honu_list_row *rows, uint8_t *keys_out, uint64_t cap,
+                           uint64_t *total, const ScanState &S, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -16,7 +16,11 @@ Codec.merge_keys (honu_key_merge). delete() is the host statement of a batch of
 Deletes from such a list (the loop of Store.Drop, store.go:378-383, and its
 DeleteBucket, store.go:399-404) and compact() of what a Put of a stored key
 does to the row it replaces; the batch form of both is Codec.delete_keys
-(honu_key_delete).
+(honu_key_delete). scan() is the host statement of what follows a Seek on
+every read path, the walk with Cursor.Next() or Cursor.Prev()
+(iterator/cursor.go:57-89) that List, Versions and Retrieve
+(collection.go:32-35, 97-110) and the loop of store.go:379 are made of, over a
+batch of seek() ranges; the batch form is Codec.list_keys (honu_key_list).
 """
 from __future__ import annotations
 
@@ -189,6 +193,39 @@ def compact(sorted_keys: Sequence[bytes]):
     n = len(sorted_keys)
     gone = [p + 1 < n and bytes(sorted_keys[p + 1]) == bytes(sorted_keys[p]) for p in range(n)]
     return ([k for k, g in zip(sorted_keys, gone) if not g], [k for k, g in zip(sorted_keys, gone) if g])
+
+
+def scan(sorted_keys: Sequence[bytes], ranges: Iterable, reverse: bool = False, limit: int = 0,
+         latest: bool = False):
+    """A batch of cursor walks over a sorted list of keys: for every (pos,
+    end) of `ranges`, as seek() gives them, the positions a cursor visits,
+    as a list of (range, pos) in output order, the ranges in the order given.
+    Forward is Cursor.Next() from pos up to end (iterator/cursor.go:57-72;
+    Collection.List, collection.go:32-35; the loop of store.go:379); `reverse`
+    is Cursor.Prev() from end - 1 down to pos (cursor.go:74-89; Versions,
+    "from the most recent version to the oldest", collection.go:106-110);
+    `limit`, when not 0, stops a walk after that many steps, so reverse with
+    limit 1 is Retrieve's "latest version" (collection.go:97-104) of an object
+    range. With `latest` a walk visits only the rows that are the last of
+    their object, the group of keys with the same first 17 bytes
+    (ObjectPrefix, keys.go:74-79), so an object whose latest version lies
+    outside the range is not visited. pos and end are clamped to the list
+    (end to its length, pos to end); ranges may be empty, overlap, repeat and
+    come in any order. Tombstones are not filtered. The batch form on the GPU
+    is Codec.list_keys (honu_key_list in include/honu_codec.h)."""
+    n = len(sorted_keys)
+    out = []
+    for q, (pos, end) in enumerate(ranges):
+        end = min(int(end), n)
+        pos = min(int(pos), end)
+        walk = range(end - 1, pos - 1, -1) if reverse else range(pos, end)
+        if latest:
+            walk = [p for p in walk if p + 1 == n or
+                    bytes(sorted_keys[p + 1])[:PREFIX_SIZE] != bytes(sorted_keys[p])[:PREFIX_SIZE]]
+        else:
+            walk = list(walk)
+        out.extend((q, p) for p in (walk[:limit] if limit else walk))
+    return out
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

@@ -65,6 +65,13 @@ SEEK_DTYPE = np.dtype(
 SEEK_NONE = 0xFFFFFFFF
 SEEK_FOUND, SEEK_END, SEEK_EXACT, SEEK_FIRST_LIVE, SEEK_LATEST_LIVE, SEEK_SKIPPED = (1 << b for b in range(6))
 DELETE_SUPERSEDED = 1 << 0  # honu_key_delete flag (Codec.delete_keys): only a run's last row stays
+# honu_list_row: one row of honu_key_list per position a cursor visits (Codec.list_keys)
+LIST_ROW_DTYPE = np.dtype(
+    {"names": ["range", "pos", "record", "flags"], "formats": ["<u4"] * 4,
+     "offsets": [0, 4, 8, 12], "itemsize": 16}
+)
+LIST_REVERSE, LIST_LATEST = 1 << 0, 1 << 1            # honu_key_list flags: Prev() from end - 1; one row per object
+LIST_ROW_HEAD, LIST_ROW_TOMBSTONE = 1 << 0, 1 << 1    # honu_list_row.flags
 
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1

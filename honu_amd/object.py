@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, INFO_DTYPE, META_DTYPE, HostBatch, Metadata, pack_batch,
-                       unpack_row)
+from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, INFO_DTYPE, LIST_LATEST, LIST_REVERSE, META_DTYPE, HostBatch,
+                       Metadata, pack_batch, unpack_row)
 
 StorageVersion = 1  # object.go:14
 
@@ -391,6 +391,37 @@ class Codec:
         torch = _torch()
         return (out[:29 * n], order_out[:4 * n].view(torch.int32) if order is not None else None,
                 valid_out[:8].view(torch.int64), removed[:8].view(torch.int64))
+
+    def list_keys(self, sorted_keys, order, valid, ranges, cap: int, limit: int = 0, reverse: bool = False,
+                  latest=None, info=None, want_keys: bool = False):
+        """A batch of cursor walks (Cursor.Next / Prev, iterator/cursor.go:57-89;
+        List, Versions, Retrieve, collection.go:32-35, 97-110; the loop of
+        store.go:379) over `ranges`, seek_keys' rows, which stay on the
+        device: every row a cursor walking [pos, end) of each range would
+        visit, packed, the ranges in order; `reverse` walks from end - 1 down,
+        `limit` (not 0) stops each walk after that many rows, `latest`
+        ((obj_off, objects) of key_objects) keeps one row per object, its last.
+        Returns (rows: honu_list_row as an int32 view of shape (cap, 4), range,
+        pos, record, flags (metadata.LIST_ROW_DTYPE), of which min(total, cap)
+        are written; range_off: int64[m + 1], the rows before each range and
+        the total; total: one int64; keys: 29 bytes per row when `want_keys`,
+        else None), all on the device. A caller that reads total > cap calls
+        again with more room. `order` (or None) gives the record indices,
+        `info` (the decode's record info; needs `order`) the TOMBSTONE flag."""
+        n = sorted_keys.numel() // 29
+        m = ranges.numel() * ranges.element_size() // 20
+        flags = (LIST_REVERSE if reverse else 0) | (LIST_LATEST if latest is not None else 0)
+        obj_off, objects = latest if latest is not None else (None, None)
+        rows = self._empty(16 * cap)
+        range_off, total = self._empty(8 * (m + 1)), self._empty(8)
+        keys = self._empty(29 * cap) if want_keys else None
+        _lib.check(self.lib.honu_key_list(
+            self.ctx, _lib.ptr(sorted_keys), _lib.ptr(order), _lib.ptr(valid), n, _lib.ptr(ranges), m, limit, flags,
+            _lib.ptr(obj_off), _lib.ptr(objects), _lib.ptr(info), _lib.ptr(range_off), _lib.ptr(rows), _lib.ptr(keys),
+            cap, _lib.ptr(total), self.stream), "honu_key_list")
+        torch = _torch()
+        return (rows[:16 * cap].view(torch.int32).view(cap, 4), range_off[:8 * (m + 1)].view(torch.int64),
+                total[:8].view(torch.int64), keys[:29 * cap] if want_keys else None)
 
 
 _default: Optional[Codec] = None

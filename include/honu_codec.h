@@ -21,6 +21,7 @@
  *   Cursor.Seek, Has, Exists    iterator/cursor.go:44-55  honu_key_seek (positions of a batch of probes)
  *   bucket.Put (a batch)        store.go:232, 395, 530 honu_key_merge (stable merge into the sorted column)
  *   bucket.Delete (a batch)     store.go:378-383, 399-404 honu_key_delete (stable compaction of the sorted column)
+ *   Cursor.Next / Prev (batch)  iterator/cursor.go:57-89  honu_key_list (the rows of a batch of seek ranges, packed)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -770,6 +771,93 @@ int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *
                         const uint64_t *d_valid_del, uint64_t m, uint32_t probe_len, uint32_t flags,
                         uint8_t *d_sorted_out, uint32_t *d_order_out, uint64_t *d_valid_out,
                         uint64_t *d_removed, void *d_work, uint64_t work_bytes, void *stream);
+
+/* honu_key_list flags */
+enum {
+    HONU_LIST_REVERSE = 1u << 0, /* Prev() from the range's last row: end-1 down to pos (Versions: most recent first) */
+    HONU_LIST_LATEST  = 1u << 1  /* one row per object: only rows that are the last of their 17-byte prefix group */
+};
+enum {                            /* honu_list_row.flags */
+    HONU_LIST_ROW_HEAD      = 1u << 0, /* first row emitted for its range */
+    HONU_LIST_ROW_TOMBSTONE = 1u << 1  /* d_info given and info[record].tombstone */
+};
+typedef struct honu_list_row {
+    uint32_t range;   /* q: which honu_seek row it came from */
+    uint32_t pos;     /* position in the sorted column */
+    uint32_t record;  /* d_order[pos]; HONU_SEEK_NONE when d_order is NULL */
+    uint32_t flags;
+} honu_list_row;      /* 16 */
+uint64_t honu_sizeof_list_row(void);
+
+/* A batch of cursor walks over the sorted key column: every reference read
+ * path after the Seek is a walk with Cursor.Next() or Cursor.Prev()
+ * (iterator/cursor.go:57-89): Collection.List() (collection.go:32-35),
+ * Versions() ("from the most recent version to the oldest",
+ * collection.go:106-110), Retrieve() ("the latest version",
+ * collection.go:97-104) and the loop `for ; key != nil &&
+ * bytes.HasPrefix(key, id[:]); key, _ = cursor.Next()` of store.go:379. For m
+ * ranges, given as the honu_seek rows honu_key_seek wrote, the call emits
+ * every row that a cursor walking each range would visit, packed, the ranges
+ * in order. Every count stays on the device.
+ * Range bounds. v = min(d_valid[0], n). Range q uses end' = min(end, v) and
+ * pos' = min(pos, end') of d_ranges[q]; a range whose flags carry
+ * HONU_SEEK_SKIPPED is empty. No other flag bit of the seek row is trusted
+ * and neither are first and latest: only pos and end are read. Ranges may
+ * overlap, repeat and come in any order.
+ * Plain mode. c_q = end' - pos', capped at limit when limit != 0 (limit
+ * stands for calling Next() that many times). The positions are pos', pos' +
+ * 1, ...; with HONU_LIST_REVERSE end' - 1, end' - 2, ... (Prev()), so limit 1
+ * with REVERSE is Retrieve's latest version of an object range.
+ * HONU_LIST_LATEST. Needs d_obj_off and d_objects as honu_key_objects wrote
+ * them for this column (objects + 1 offsets, d_obj_off[objects] = valid; room
+ * for n + 1 values). It reads objects = min(d_objects[0], n) and clamps every
+ * offset to v. The candidate rows are L_j = d_obj_off[j + 1] - 1, each
+ * object's last row; range q emits the L_j with pos' <= L_j < end', ascending
+ * j, descending with REVERSE, and limit applies after that. An object whose
+ * latest version lies outside the range is not emitted.
+ * Tombstones. Collection.Delete's comment says an object with a tombstone
+ * version "will not be returned in list queries" (collection.go:132-134).
+ * Here a tombstone is FLAGGED (HONU_LIST_ROW_TOMBSTONE, when d_info is
+ * given), not filtered: the filter is not built, and neither is a gather of
+ * the record values themselves.
+ * Outputs. d_range_off[0, m] is the exclusive scan of the c_q and
+ * d_range_off[m] = d_total[0] = total, a 64-bit sum (overlapping ranges can
+ * exceed n). w = min(total, cap): only output rows g < w are written. Row g
+ * belongs to the range q with d_range_off[q] <= g < d_range_off[q + 1] and
+ * its position is the (g - d_range_off[q])-th of that range; HEAD is set on
+ * the 0-th. d_rows[g] is written whole; d_keys_out + 29 g, when given,
+ * receives the 29 bytes of the column's row (Cursor.Key()'s copy). A caller
+ * that sees total > cap re-issues with more room. The write set is exactly
+ * d_range_off[0, m + 1), d_total[0], d_rows[0, w) and d_keys_out[0, 29 w).
+ * Optionals. d_order, d_info and d_keys_out may be NULL; d_info needs
+ * d_order. Without d_order, record is HONU_SEEK_NONE. An index of d_order
+ * that is not below n reads d_info row n - 1, as in honu_key_seek. d_rows may
+ * be NULL only with cap == 0: a counting call. With m == 0, d_range_off[0] =
+ * 0 and d_total[0] = 0; with v == 0 every count is 0.
+ * Asynchronous on `stream`, no host synchronisation, no allocation, no
+ * workspace; replays from a captured graph, also after the counts and seek
+ * rows were changed on the device between replays. The counts are scanned in
+ * place in d_range_off by the context's scan (the one behind
+ * honu_exclusive_scan), so one context serves one stream at a time, as for
+ * honu_sort_keys and honu_key_delete. Garbage in d_ranges or d_obj_off may
+ * give wrong rows, never an access outside the n rows or a search that does
+ * not end.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for n, m or cap above
+ * 2^32 - 1, or for m + 1 above honu_ctx_max_records; HONU_E_ARG for a NULL
+ * ctx, d_valid, d_range_off or d_total, a NULL d_ranges with m > 0, a NULL
+ * d_sorted with n > 0, a NULL d_rows with cap > 0, unknown flag bits, LATEST
+ * without both d_obj_off and d_objects, d_info without d_order, or a
+ * misaligned pointer (4 bytes: d_ranges, d_order; 8 bytes: d_valid,
+ * d_objects, d_obj_off, d_range_off, d_total, d_info; 16 bytes: d_rows).
+ * The get-only params are "list_tile" (output rows per workgroup) and
+ * "list_stage" (range offsets a workgroup stages in LDS). */
+int32_t honu_key_list(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_order,
+                      const uint64_t *d_valid, uint64_t n,
+                      const honu_seek *d_ranges, uint64_t m, uint32_t limit, uint32_t flags,
+                      const uint64_t *d_obj_off, const uint64_t *d_objects,   /* LATEST only */
+                      const honu_record_info *d_info,
+                      uint64_t *d_range_off, honu_list_row *d_rows, uint8_t *d_keys_out,
+                      uint64_t cap, uint64_t *d_total, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
