@@ -11,27 +11,27 @@
 //          (HONU_DELETE_SUPERSEDED) when the next valid row has its 29 bytes.
 //          The tile's rows are a contiguous key range, so the delete rows that
 //          can match any of them are one range of the list: its two ends are
-//          found once per workgroup, a wave each, 64 mids per step (as
-//          merge_split does), and the range is staged packed and masked
-//          (keypack.h) in LDS, 9 words per row, an odd stride, when it has no
-//          more than DELETE_STAGE rows; a longer one is searched in global
-//          memory. A row's lower bound in the range decides it. The successor
-//          comes from the next lane, for lane 63 from memory (it may be the
-//          next tile's). The tile writes its keep mask, one ballot per 64
-//          rows, and its kept count;
+//          found once per workgroup, a wave each (wave_bound), and the
+//          range is staged packed and masked in LDS (keycol.h's 9-word row)
+//          when it has no more than DELETE_STAGE rows; a longer one is
+//          searched in global memory. A row's lower bound in the range
+//          (thread_bound) decides it. The successor comes from the next
+//          lane, for lane 63 from memory (it may be the next tile's). The
+//          tile writes its keep mask, one ballot per 64 rows, and its kept
+//          count;
 //   scan   launch_scan over the tiles' kept counts, the total to d_valid_out
 //          (the context's scan state covers max_records rows: honu_key_delete
 //          refuses a column of more tiles than that);
 //   place  a row's rank in its tile is a popcount of the mask below it; a
 //          kept row goes to kept_before_tile + rank, a removed row p to
 //          kept + (p - kept_before_p), a tail row stays. Rows move as their
-//          bytes: two overlapping 16-byte loads and stores.
+//          bytes (copy_key).
 // The new kernels have no atomics, no spin-wait and no state outside the
 // launch; launch_scan is the only step in which workgroups depend on each
 // other. Every position derived from a count on the device is clamped to the
 // n / m rows.
 #include "kernels.h"
-#include "keypack.h"
+#include "keycol.h"
 
 namespace honu {
 
@@ -39,7 +39,6 @@ constexpr uint32_t DELETE_TILE = 1024;                                   // colu
 constexpr uint32_t DELETE_WORDS = DELETE_TILE / HONU_WAVE;               // ballots per tile
 constexpr uint32_t DELETE_ROUNDS = DELETE_WORDS / HONU_WAVES_PER_BLOCK;  // ballots per wave
 constexpr uint32_t DELETE_STAGE = 1024;                                  // delete rows a workgroup stages
-constexpr uint32_t DELETE_ROW = SORT_KEY_WORDS + 1;                      // LDS words per staged row (odd)
 // 1024 x 36 bytes: 36 KiB, four workgroups per CU (measured against 2048 rows, two workgroups per CU,
 // and against no stage at all: DESIGN §6.4)
 static_assert(DELETE_TILE % (HONU_WAVE * HONU_WAVES_PER_BLOCK) == 0, "a wave takes whole ballots");
@@ -47,8 +46,6 @@ static_assert(DELETE_WORDS <= HONU_BLOCK, "a thread per ballot in the place kern
 
 uint32_t delete_tile() { return DELETE_TILE; }
 uint64_t delete_tiles(uint64_t n) { return (n + DELETE_TILE - 1) / DELETE_TILE; }
-
-static uint64_t up256(uint64_t x) { return (x + 255) & ~255ull; }
 
 // the keep masks (DELETE_WORDS words per tile), then the kept counts (a word per tile)
 uint64_t delete_workspace_bytes(uint64_t n) {
@@ -72,59 +69,26 @@ HONU_DEV void delete_load(const uint8_t *col, uint32_t i, const SeekMask &M, uin
     load_masked(col + (uint64_t)HONU_KEY_LEN * i, M, w);
 }
 
-// a < b (or_equal: a <= b) by bytes.Compare (word 0 is the most significant)
-HONU_DEV bool delete_before(const uint32_t a[SORT_KEY_WORDS], const uint32_t b[SORT_KEY_WORDS], bool or_equal) {
-    bool lt = or_equal;
-#pragma unroll
-    for (int i = SORT_KEY_WORDS - 1; i >= 0; i--) lt = a[i] != b[i] ? a[i] < b[i] : lt;
-    return lt;
-}
-
-HONU_DEV bool delete_same(const uint32_t a[SORT_KEY_WORDS], const uint32_t b[SORT_KEY_WORDS]) {
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < SORT_KEY_WORDS; i++) eq = eq && a[i] == b[i];
-    return eq;
-}
-
-HONU_DEV uint32_t delete_valid(const uint64_t *valid, uint32_t n) { return (uint32_t)(*valid < n ? *valid : n); }
-
 // How many of the delete rows [0, vd) are below k (upper: below or equal) over
-// the masked prefixes: the lower (upper) bound of k in the list. Called by a
-// whole wave with one k; each step the 64 lanes ask 64 evenly spaced mids and
-// the bracket shrinks 64-fold, as in merge_split (merge.hip). The rows that
-// say yes are the ones below the bound; whatever the list holds, lo and hi
-// stay inside [0, vd] and the bracket shrinks every step.
+// the masked prefixes: the lower (upper) bound of k in the list, by a whole
+// wave with one k
 HONU_DEV uint32_t delete_bound(const uint8_t *__restrict__ del, uint32_t vd, const SeekMask &M,
                                const uint32_t k[SORT_KEY_WORDS], bool upper) {
-    uint32_t lo = 0, hi = vd;
-    const uint32_t lane = lane_id();
-    while (lo < hi) {  // (wave-uniform)
-        const uint32_t s = hi - lo;
-        auto mid_of = [&](uint32_t l) { return s > HONU_WAVE ? lo + (uint32_t)(((uint64_t)l * s) >> 6) : lo + l; };
-        const uint32_t mid = mid_of(lane);
-        bool yes = false;
-        if (mid < hi) {
-            uint32_t d[SORT_KEY_WORDS];
-            delete_load(del, mid, M, d);
-            yes = delete_before(d, k, upper);
-        }
-        const uint32_t t = (uint32_t)__popcll(__ballot(yes));  // the first t lanes
-        const uint32_t above = t < HONU_WAVE ? mid_of(t) : hi;
-        lo = t ? mid_of(t - 1) + 1 : lo;
-        hi = above < hi ? above : hi;
-    }
-    return lo;
+    return wave_bound(0, vd, [&](uint32_t mid) {
+        uint32_t d[SORT_KEY_WORDS];
+        delete_load(del, mid, M, d);
+        return packed_before(d, k, upper);
+    });
 }
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_delete_mark(
     const uint8_t *__restrict__ sorted, const uint64_t *__restrict__ valid, uint32_t n,
     const uint8_t *__restrict__ del, const uint64_t *__restrict__ valid_del, uint32_t m, SeekMask M,
     uint32_t flags, DeleteWork W) {
-    __shared__ uint32_t rows[DELETE_STAGE * DELETE_ROW];
+    __shared__ uint32_t rows[DELETE_STAGE * KEY_ROW_WORDS];
     __shared__ uint32_t range[2];
     __shared__ uint32_t cnt[HONU_WAVES_PER_BLOCK];
-    const uint32_t v = delete_valid(valid, n), vd = m ? delete_valid(valid_del, m) : 0;
+    const uint32_t v = valid_rows(valid, n), vd = m ? valid_rows(valid_del, m) : 0;
     const uint32_t p0 = blockIdx.x * DELETE_TILE;  // below n
     const uint32_t len = n - p0 < DELETE_TILE ? n - p0 : DELETE_TILE;
     const uint32_t vlen = p0 < v ? (v - p0 < len ? v - p0 : len) : 0;  // the tile's valid rows: its first vlen
@@ -149,8 +113,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_delete_mark(
         for (uint32_t r = threadIdx.x; r < dn; r += HONU_BLOCK) {
             uint32_t d[SORT_KEY_WORDS];
             delete_load(del, lo + r, M, d);
-#pragma unroll
-            for (int i = 0; i < SORT_KEY_WORDS; i++) rows[r * DELETE_ROW + i] = d[i];
+            lds_row_store(rows, r, d);
         }
         __syncthreads();
     }
@@ -172,23 +135,16 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_delete_mark(
 #pragma unroll
                 for (int i = 0; i < SORT_KEY_WORDS; i++) k[i] = w[i] & M.w[i];
                 auto load = [&](uint32_t at) {
-                    if (staged) {
-#pragma unroll
-                        for (int i = 0; i < SORT_KEY_WORDS; i++) d[i] = rows[at * DELETE_ROW + i];
-                    } else {
-                        delete_load(del, lo + at, M, d);
-                    }
+                    if (staged) lds_row_load(rows, at, d);
+                    else delete_load(del, lo + at, M, d);
                 };
-                uint32_t a = 0, b = dn;  // the lower bound of k in the range
-                while (a < b) {
-                    const uint32_t mid = a + ((b - a) >> 1);
+                const uint32_t a = thread_bound(0, dn, [&](uint32_t mid) {  // the lower bound of k in the range
                     load(mid);
-                    if (delete_before(d, k, false)) a = mid + 1;
-                    else b = mid;
-                }
+                    return packed_before(d, k, false);
+                });
                 if (a < dn) {
                     load(a);
-                    drop = delete_same(d, k);
+                    drop = packed_same(d, k);
                 }
             }
             if (flags & HONU_DELETE_SUPERSEDED) {
@@ -199,7 +155,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_delete_mark(
                 const bool has_next = in && v - p0 - t > 1;  // p + 1 < v
                 if (lane == HONU_WAVE - 1 && has_next)
                     pack_key(sorted + (uint64_t)HONU_KEY_LEN * (p0 + t + 1), true, nx);
-                drop = drop || (has_next && delete_same(w, nx));
+                drop = drop || (has_next && packed_same(w, nx));
             }
             keep = in && !drop;
         }
@@ -224,7 +180,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_delete_place(
     const uint64_t *__restrict__ kept_total, uint64_t *__restrict__ removed, DeleteWork W) {
     __shared__ uint64_t msk[DELETE_WORDS];
     __shared__ uint32_t pre[DELETE_WORDS];  // rows kept in the tile's ballots before ballot j
-    const uint32_t v = delete_valid(valid, n);
+    const uint32_t v = valid_rows(valid, n);
     const uint64_t kept = *kept_total < v ? *kept_total : v;
     if (blockIdx.x == 0 && threadIdx.x == 0 && removed) *removed = v - kept;
     const uint32_t p0 = blockIdx.x * DELETE_TILE;  // below n
@@ -251,11 +207,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_delete_place(
             dst = (msk[j] >> lane) & 1ull ? kept_before : kept + ((uint64_t)p - kept_before);
             dst = dst < v ? dst : p;  // (a mask or a count that is not the mark's: inside the rows all the same)
         }
-        const uint8_t *k = sorted + (uint64_t)HONU_KEY_LEN * p;
-        const u32x4 x = *reinterpret_cast<const u32x4u *>(k), y = *reinterpret_cast<const u32x4u *>(k + 13);
-        uint8_t *o = out + (uint64_t)HONU_KEY_LEN * dst;
-        *reinterpret_cast<u32x4u *>(o) = x;
-        *reinterpret_cast<u32x4u *>(o + 13) = y;
+        copy_key(out + (uint64_t)HONU_KEY_LEN * dst, sorted + (uint64_t)HONU_KEY_LEN * p);
         if (order_out) order_out[dst] = order[p];
     }
 }

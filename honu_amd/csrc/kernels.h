@@ -236,6 +236,9 @@ uint64_t scan_status_words(uint64_t n);
 hipError_t launch_scan(const uint64_t *in, uint64_t n, int K, uint64_t *out, uint64_t *totals,
                        const ScanState &S, hipStream_t s);
 
+// a workspace's parts start on 256-byte boundaries
+inline uint64_t up256(uint64_t x) { return (x + 255) & ~255ull; }
+
 // sort.hip: sort.Sort(keys.Keys) (keys.go:126-130) and the objects' version
 // ranges (keys.go:73-92). The caller's workspace, carved: the plan words, the
 // two sides of packed keys (32 bytes each) and indices, the one scan column

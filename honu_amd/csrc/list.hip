@@ -21,23 +21,24 @@
 //           output rows (the grid is sized from cap and strides over the
 //           tiles; a tile at or past min(total, cap) ends the workgroup). The
 //           ranges of the tile's first and last row are two upper bounds over
-//           d_range_off, a wave each, 64 mids per step (as merge_split and
-//           delete_bound do). A slice of at most LIST_STAGE ranges is staged
-//           in LDS, per range its 32-bit offset from the tile's first row
-//           and where its walk starts (pos', end', or with LATEST the object
-//           found by one binary search per non-empty range, not per row),
-//           and every row searches the offsets there; a longer slice (a run
-//           of empty ranges inside one tile) is searched in global memory. A
-//           row then has its range q and its index k in it: its position is
+//           d_range_off, a wave each (wave_bound, keycol.h). A slice of at
+//           most LIST_STAGE ranges is staged in LDS, per range its 32-bit
+//           offset from the tile's first row and where its walk starts (pos',
+//           end', or with LATEST the object found by one binary search per
+//           non-empty range, not per row), and every row searches the offsets
+//           there (thread_bound); a longer slice (a run of empty ranges inside
+//           one tile) is searched in global memory. A row then has its range
+//           q and its index k in it: its position is
 //           pos' + k, end' - 1 - k, or through d_obj_off for LATEST. The
-//           16-byte row goes out in one vector store, the key as two
-//           overlapping 16-byte loads and stores (as k_delete_place moves it).
+//           16-byte row goes out in one vector store, the key as its bytes
+//           (copy_key).
 // The kernels have no atomics, no spin-wait and no state outside the launch;
 // launch_scan is the only step in which workgroups depend on each other. Every
 // position derived from a count or offset read on the device is clamped to the
 // n / m / v rows: garbage in d_ranges or d_obj_off may give wrong rows, never
 // an access out of bounds or a search that does not end.
 #include "kernels.h"
+#include "keycol.h"
 
 namespace honu {
 
@@ -59,8 +60,6 @@ struct ListRange {
     uint32_t pos, end;  // pos <= end <= v
 };
 
-HONU_DEV uint32_t list_valid(const uint64_t *valid, uint32_t n) { return (uint32_t)(*valid < n ? *valid : n); }
-
 // range q clamped to the valid rows; empty when the seek skipped the probe
 HONU_DEV ListRange list_range(const honu_seek *__restrict__ ranges, uint32_t q, uint32_t v) {
     const uint32_t pos = ranges[q].pos, end = ranges[q].end, skipped = ranges[q].flags & HONU_SEEK_SKIPPED;
@@ -72,20 +71,12 @@ HONU_DEV ListRange list_range(const honu_seek *__restrict__ ranges, uint32_t q, 
 }
 
 // How many of the objects [0, objects) have their end, d_obj_off[j + 1] clamped to v, at or below x: the
-// object whose latest row is the first at or past x. lo and hi stay inside [0, objects] whatever the offsets hold
+// object whose latest row is the first at or past x
 HONU_DEV uint32_t list_objects_below(const uint64_t *__restrict__ obj_off, uint32_t objects, uint32_t v, uint32_t x) {
-    uint32_t lo = 0, hi = objects;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
+    return thread_bound(0, objects, [&](uint32_t mid) {
         const uint64_t e = obj_off[(uint64_t)mid + 1];
-        if ((e < v ? (uint32_t)e : v) <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-HONU_DEV uint32_t list_objects(const uint64_t *objects, uint32_t n) {
-    return (uint32_t)(*objects < n ? *objects : n);
+        return (e < v ? (uint32_t)e : v) <= x;
+    });
 }
 
 // Where the walk of range R starts: the row pos (forward) or the row before end (REVERSE: end itself is
@@ -105,11 +96,11 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_list_count(
     if (q > m) return;
     uint32_t c = 0;
     if (q < m) {
-        const uint32_t v = list_valid(valid, n);
+        const uint32_t v = valid_rows(valid, n);
         const ListRange R = list_range(ranges, (uint32_t)q, v);
         if (flags & HONU_LIST_LATEST) {
             // the latest rows L_j = off[j + 1] - 1 with pos <= L_j < end: pos < off[j + 1] <= end
-            const uint32_t objs = list_objects(objects, n);
+            const uint32_t objs = valid_rows(objects, n);
             const uint32_t a = list_objects_below(obj_off, objs, v, R.pos), b = list_objects_below(obj_off, objs, v, R.end);
             c = b > a ? b - a : 0;
         } else {
@@ -120,24 +111,9 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_list_count(
     range_off[q] = c;
 }
 
-// How many of off[0, m) are at or below g, by a whole wave with one g: each step the 64 lanes ask 64 evenly
-// spaced mids and the bracket shrinks 64-fold, as in delete_bound (delete.hip). Whatever off holds, lo and hi
-// stay inside [0, m] and the bracket shrinks every step.
+// How many of off[0, m) are at or below g, by a whole wave with one g
 HONU_DEV uint32_t list_bound(const uint64_t *__restrict__ off, uint32_t m, uint64_t g) {
-    uint32_t lo = 0, hi = m;
-    const uint32_t lane = lane_id();
-    while (lo < hi) {  // (wave-uniform)
-        const uint32_t s = hi - lo;
-        auto mid_of = [&](uint32_t l) { return s > HONU_WAVE ? lo + (uint32_t)(((uint64_t)l * s) >> 6) : lo + l; };
-        const uint32_t mid = mid_of(lane);
-        const bool yes = mid < hi && off[mid] <= g;
-        const uint32_t t = (uint32_t)__popcll(__ballot(yes));  // the first t lanes
-        const uint32_t above = t < HONU_WAVE ? mid_of(t) : hi;
-        lo = t ? mid_of(t - 1) + 1 : lo;
-        hi = above < hi ? above : hi;
-        lo = lo < hi ? lo : hi;
-    }
-    return lo;
+    return wave_bound(0, m, [&](uint32_t mid) { return off[mid] <= g; });
 }
 
 // range_off scanned (range_off[q] the rows before range q), *total_p the total
@@ -151,10 +127,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_list_expand(
     __shared__ uint32_t rel[LIST_STAGE];   // the slice's offsets less the tile's first row, within [0, LIST_TILE]
     __shared__ uint32_t base[LIST_STAGE];  // where each of the slice's walks starts (list_base)
     __shared__ uint32_t ends[2];
-    const uint32_t v = list_valid(valid, n);
+    const uint32_t v = valid_rows(valid, n);
     const uint64_t total = *total_p;
     const uint32_t w = (uint32_t)(total < cap ? total : cap);  // rows written
-    const uint32_t objs = flags & HONU_LIST_LATEST ? list_objects(objects, n) : 0;
+    const uint32_t objs = flags & HONU_LIST_LATEST ? valid_rows(objects, n) : 0;
     const uint32_t wv = wave_in_block(), lane = lane_id();
     for (uint64_t tile = blockIdx.x; tile * LIST_TILE < w; tile += gridDim.x) {  // (block-uniform; n, m >= 1 here)
         const uint32_t g0 = (uint32_t)(tile * LIST_TILE);
@@ -183,13 +159,8 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_list_expand(
             if (t >= len) break;
             const uint32_t g = g0 + t;
             // the last i in [0, qn) with offset <= g (entry 0 is: the tile's first row lies in range q0)
-            uint32_t a = 1, b = qn;
-            while (a < b) {
-                const uint32_t mid = a + ((b - a) >> 1);
-                const bool le = staged ? rel[mid] <= t : range_off[q0 + mid] <= g;
-                if (le) a = mid + 1;
-                else b = mid;
-            }
+            const uint32_t a = thread_bound(
+                1, qn, [&](uint32_t mid) { return staged ? rel[mid] <= t : range_off[q0 + mid] <= g; });
             const uint32_t i = a - 1, q = q0 + i;  // q < m
             // the row's index in its range (rel[i] is exact for i > 0: q0 is the last range that starts at or before g0)
             const uint64_t before = i == 0 ? before0 : (staged ? (uint64_t)g0 + rel[i] : range_off[q]);
@@ -211,17 +182,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_list_expand(
             if (order) {
                 const uint32_t rec = order[p];
                 row[2] = rec;
-                // (an index is below n in an order honu_sort_keys wrote; whatever else it holds reads row n - 1)
-                if (info && info[rec < n ? rec : n - 1].tombstone) row[3] |= HONU_LIST_ROW_TOMBSTONE;
+                if (info && info[order_index(rec, n)].tombstone) row[3] |= HONU_LIST_ROW_TOMBSTONE;
             }
             *reinterpret_cast<u32x4 *>(rows + g) = row;
-            if (keys_out) {
-                const uint8_t *key = sorted + (uint64_t)HONU_KEY_LEN * p;
-                const u32x4 x = *reinterpret_cast<const u32x4u *>(key), y = *reinterpret_cast<const u32x4u *>(key + 13);
-                uint8_t *o = keys_out + (uint64_t)HONU_KEY_LEN * g;
-                *reinterpret_cast<u32x4u *>(o) = x;
-                *reinterpret_cast<u32x4u *>(o + 13) = y;
-            }
+            if (keys_out) copy_key(keys_out + (uint64_t)HONU_KEY_LEN * g, sorted + (uint64_t)HONU_KEY_LEN * p);
         }
         __syncthreads();  // rel and ends are rewritten by the next tile
     }

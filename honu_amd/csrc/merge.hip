@@ -8,15 +8,14 @@
 // are on the device, so a workgroup decides there what its tile is: positions
 // below va + vb are merged, the rest copied from the two invalid tails.
 //   partition  the tile's first and last diagonal are split by a search over
-//              global memory (merge path), each workgroup its own two, a
-//              wave each: nothing passes between workgroups;
-//   stage      the A range and the B range of the tile packed (keypack.h)
-//              into LDS, the index beside the key: 9 words per row, an odd
-//              stride, so rows r and r + 1 lie in different banks;
+//              global memory (merge path, a wave_bound), each workgroup its
+//              own two, a wave each: nothing passes between workgroups;
+//   stage      the A range and the B range of the tile packed into LDS, the
+//              index beside the key (keycol.h's 9-word row);
 //   rank       a row's output position is its offset in its own range plus
-//              the rows of the other range that go before it, one binary
-//              search in LDS: strictly below it for an A row, below or equal
-//              for a B row, the partition's tie rule;
+//              the rows of the other range that go before it, one
+//              thread_bound in LDS: strictly below it for an A row, below or
+//              equal for a B row, the partition's tie rule;
 //   emit       the ranks turned round in LDS (rank -> staged row), so that
 //              consecutive lanes store consecutive output rows.
 // (Measured against a per-thread serial merge of four consecutive outputs
@@ -25,12 +24,11 @@
 // nearly every tile is A's alone. DESIGN §6.3.)
 // No atomics, no spin-wait, no state outside the launch.
 #include "kernels.h"
-#include "keypack.h"
+#include "keycol.h"
 
 namespace honu {
 
 constexpr uint32_t MERGE_TILE = 1024;                 // output positions per workgroup
-constexpr uint32_t MERGE_ROW = SORT_KEY_WORDS + 1;    // LDS words per staged row: the packed key, the index
 // 1024 x 36 bytes of rows + 2 KiB of ranks + the splits: 38 KiB, four workgroups per CU
 static_assert(MERGE_TILE <= 65536, "the ranks are 16-bit");
 static_assert(MERGE_TILE % HONU_BLOCK == 0, "a thread takes MERGE_TILE / HONU_BLOCK positions");
@@ -41,58 +39,20 @@ HONU_DEV void load_packed(const uint8_t *col, uint32_t i, uint32_t w[SORT_KEY_WO
     pack_key(col + (uint64_t)HONU_KEY_LEN * i, true, w);
 }
 
-// a <= b by bytes.Compare (word 0 is the most significant)
-HONU_DEV bool packed_le(const uint32_t a[SORT_KEY_WORDS], const uint32_t b[SORT_KEY_WORDS]) {
-    bool le = true;
-#pragma unroll
-    for (int i = SORT_KEY_WORDS - 1; i >= 0; i--) le = a[i] != b[i] ? a[i] < b[i] : le;
-    return le;
-}
-
 // How many of the first d merged rows (d <= va + vb) come from A: the i with
 // A[i - 1] <= B[d - i] and B[d - i - 1] < A[i], rows out of range counting as
 // -inf / +inf. A[mid] is among the first d exactly when it goes before
 // B[d - 1 - mid], and on equal keys it does; the mids that say yes are the
-// ones below i. Called by a whole wave with one d: a bisection whose every
-// step is a round trip to memory would take 20 of them over 1M rows, so each
-// step the 64 lanes ask 64 evenly spaced mids at once and the bracket shrinks
-// 64-fold: four round trips (measured against the one-lane bisection: DESIGN §6.3).
+// ones below i. Called by a whole wave with one d: four round trips over 1M
+// rows (measured against the one-lane bisection: DESIGN §6.3).
 HONU_DEV uint32_t merge_split(const uint8_t *__restrict__ a, uint32_t va, const uint8_t *__restrict__ b,
                               uint32_t vb, uint32_t d) {
-    uint32_t lo = d > vb ? d - vb : 0, hi = d < va ? d : va;
-    const uint32_t lane = lane_id();
-    while (lo < hi) {  // (wave-uniform)
-        const uint32_t s = hi - lo;
-        // lane l's mid: lo + floor(l s / 64) over a bracket of more than 64 (distinct, lo the first), else lo + l
-        auto mid_of = [&](uint32_t l) { return s > HONU_WAVE ? lo + (uint32_t)(((uint64_t)l * s) >> 6) : lo + l; };
-        const uint32_t mid = mid_of(lane);
-        bool yes = false;
-        if (mid < hi) {  // lo <= mid < hi: mid < va, 0 <= d - 1 - mid < vb
-            uint32_t ka[SORT_KEY_WORDS], kb[SORT_KEY_WORDS];
-            load_packed(a, mid, ka);
-            load_packed(b, d - 1 - mid, kb);
-            yes = packed_le(ka, kb);
-        }
-        const uint32_t t = (uint32_t)__popcll(__ballot(yes));  // the first t lanes
-        const uint32_t above = t < HONU_WAVE ? mid_of(t) : hi;
-        lo = t ? mid_of(t - 1) + 1 : lo;
-        hi = above < hi ? above : hi;
-    }
-    return lo;
-}
-
-// the packed key -> key bytes [0,16) and [13,29) as little-endian words (key
-// byte j is packed byte j + 1), stored as k_sort_emit stores them
-HONU_DEV void store_packed(uint8_t *out, const uint32_t w[SORT_KEY_WORDS]) {
-    uint32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int pa = j + 1, pb = j + 14;
-        a[j >> 2] |= ((w[pa >> 2] >> (8 * (3 - (pa & 3)))) & 0xFFu) << (8 * (j & 3));
-        b[j >> 2] |= ((w[pb >> 2] >> (8 * (3 - (pb & 3)))) & 0xFFu) << (8 * (j & 3));
-    }
-    *reinterpret_cast<u32x4u *>(out) = u32x4{a[0], a[1], a[2], a[3]};
-    *reinterpret_cast<u32x4u *>(out + 13) = u32x4{b[0], b[1], b[2], b[3]};
+    return wave_bound(d > vb ? d - vb : 0, d < va ? d : va, [&](uint32_t mid) {  // mid < va, 0 <= d - 1 - mid < vb
+        uint32_t ka[SORT_KEY_WORDS], kb[SORT_KEY_WORDS];
+        load_packed(a, mid, ka);
+        load_packed(b, d - 1 - mid, kb);
+        return packed_before(ka, kb, true);
+    });
 }
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_key_merge(
@@ -100,10 +60,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_key_merge(
     uint32_t na, const uint8_t *__restrict__ sb, const uint32_t *__restrict__ ob,
     const uint64_t *__restrict__ valid_b, uint32_t nb, uint32_t b_base, uint8_t *__restrict__ out,
     uint32_t *__restrict__ order, uint64_t *__restrict__ valid_out) {
-    __shared__ uint32_t rows[MERGE_TILE * MERGE_ROW];
+    __shared__ uint32_t rows[MERGE_TILE * KEY_ROW_WORDS];  // the packed key, the index beside it
     __shared__ uint16_t at[MERGE_TILE];  // rank in the tile -> staged row
     __shared__ uint32_t split[2];
-    const uint32_t va = (uint32_t)(*valid_a < na ? *valid_a : na), vb = (uint32_t)(*valid_b < nb ? *valid_b : nb);
+    const uint32_t va = valid_rows(valid_a, na), vb = valid_rows(valid_b, nb);
     const uint32_t v = va + vb, n = na + nb;  // n <= 2^32 - 1 (launch_key_merge's caller)
     if (blockIdx.x == 0 && threadIdx.x == 0) *valid_out = v;
     const uint32_t p0 = blockIdx.x * MERGE_TILE;  // below n
@@ -127,40 +87,30 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_key_merge(
             const uint32_t src = from_a ? i0 + r : j0 + (r - la);
             uint32_t w[SORT_KEY_WORDS];
             load_packed(from_a ? sa : sb, src, w);
-            uint32_t *row = rows + r * MERGE_ROW;
-#pragma unroll
-            for (int i = 0; i < SORT_KEY_WORDS; i++) row[i] = w[i];
-            row[SORT_KEY_WORDS] = order ? (from_a ? oa[src] : ob[src] + b_base) : 0;
+            lds_row_store(rows, r, w);
+            rows[r * KEY_ROW_WORDS + SORT_KEY_WORDS] = order ? (from_a ? oa[src] : ob[src] + b_base) : 0;
         }
         __syncthreads();
         for (uint32_t r = threadIdx.x; r < len; r += HONU_BLOCK) {
             const bool from_a = r < la;
             uint32_t w[SORT_KEY_WORDS];
-#pragma unroll
-            for (int i = 0; i < SORT_KEY_WORDS; i++) w[i] = rows[r * MERGE_ROW + i];
+            lds_row_load(rows, r, w);
             // an A row: the B rows below it; a B row: the A rows below or equal to it
-            uint32_t lo = from_a ? la : 0, hi = from_a ? len : la;
-            const uint32_t first = lo;
-            while (lo < hi) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
+            const uint32_t first = from_a ? la : 0;
+            const uint32_t bound = thread_bound(first, from_a ? len : la, [&](uint32_t mid) {
                 uint32_t k[SORT_KEY_WORDS];
-#pragma unroll
-                for (int i = 0; i < SORT_KEY_WORDS; i++) k[i] = rows[mid * MERGE_ROW + i];
-                const bool before = from_a ? !packed_le(w, k) : packed_le(k, w);  // k < w : k <= w
-                if (before) lo = mid + 1;
-                else hi = mid;
-            }
-            at[(from_a ? r : r - la) + (lo - first)] = (uint16_t)r;
+                lds_row_load(rows, mid, k);
+                return packed_before(k, w, !from_a);
+            });
+            at[(from_a ? r : r - la) + (bound - first)] = (uint16_t)r;
         }
         __syncthreads();
         for (uint32_t q = threadIdx.x; q < len; q += HONU_BLOCK) {
-            const uint32_t *row = rows + (uint32_t)at[q] * MERGE_ROW;
+            const uint32_t r = at[q], p = d0 + q;
             uint32_t w[SORT_KEY_WORDS];
-#pragma unroll
-            for (int i = 0; i < SORT_KEY_WORDS; i++) w[i] = row[i];
-            const uint32_t p = d0 + q;
-            store_packed(out + (uint64_t)HONU_KEY_LEN * p, w);
-            if (order) order[p] = row[SORT_KEY_WORDS];
+            lds_row_load(rows, r, w);
+            unpack_key(out + (uint64_t)HONU_KEY_LEN * p, w);
+            if (order) order[p] = rows[r * KEY_ROW_WORDS + SORT_KEY_WORDS];
         }
     }
 
@@ -172,11 +122,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_key_merge(
         const uint32_t p = p0 + t, q = p - v;
         const bool from_a = q < ta;
         const uint32_t src = from_a ? va + q : vb + (q - ta);
-        const uint8_t *k = (from_a ? sa : sb) + (uint64_t)HONU_KEY_LEN * src;
-        const u32x4 x = *reinterpret_cast<const u32x4u *>(k), y = *reinterpret_cast<const u32x4u *>(k + 13);
-        uint8_t *o = out + (uint64_t)HONU_KEY_LEN * p;
-        *reinterpret_cast<u32x4u *>(o) = x;
-        *reinterpret_cast<u32x4u *>(o + 13) = y;
+        copy_key(out + (uint64_t)HONU_KEY_LEN * p, (from_a ? sa : sb) + (uint64_t)HONU_KEY_LEN * src);
         if (order) order[p] = from_a ? oa[src] : ob[src] + b_base;
     }
 }

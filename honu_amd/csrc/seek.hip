@@ -4,7 +4,7 @@
 // ends of an object's range [ObjectPrefix, ObjectLimit) (keys/keys.go:73-92).
 //
 // A probe is the first probe_len bytes of a 29-byte row. Keys and probes are
-// compared in the sort's packed form (keypack.h) under a mask that clears the
+// compared in the sort's packed form (keycol.h) under a mask that clears the
 // bytes past probe_len: big-endian words, unsigned, which is bytes.Compare of
 // the probe_len-byte prefixes. A key that has the probe as a proper prefix is
 // greater than the probe, so Seek's position is the lower bound over the
@@ -21,7 +21,7 @@
 // starts from what is left (nothing, for a probe that is not stored).
 // No atomics, no spin-wait, no state outside the launch.
 #include "kernels.h"
-#include "keypack.h"
+#include "keycol.h"
 
 namespace honu {
 
@@ -39,14 +39,6 @@ constexpr uint64_t SEEK_AUTO_KEYS = 65536;
 uint32_t seek_fence() { return SEEK_FENCE; }
 uint64_t seek_auto_probes() { return SEEK_AUTO_PROBES; }
 uint64_t seek_auto_keys() { return SEEK_AUTO_KEYS; }
-
-// bytes.Compare of two packed keys: -1, 0, 1 (word 0 is the most significant)
-HONU_DEV int cmp_packed(const uint32_t k[SORT_KEY_WORDS], const uint32_t p[SORT_KEY_WORDS]) {
-    int c = 0;
-#pragma unroll
-    for (int i = SORT_KEY_WORDS - 1; i >= 0; i--) c = k[i] != p[i] ? (k[i] < p[i] ? -1 : 1) : c;
-    return c;
-}
 
 // pos: the first position in [lo, hi] whose key is >= p; end: the first in
 // [ulo, uhi] whose key is > p. The caller knows both brackets to hold their
@@ -100,8 +92,7 @@ HONU_DEV void seek_finish(honu_seek *out, uint32_t pos, uint32_t end, uint32_t v
             first = order[pos];
             latest = order[end - 1];
             if (info) {
-                // (an index is below n in an order honu_sort_keys wrote; whatever else it holds reads row n - 1)
-                const uint64_t i = first < n ? first : n - 1, j = latest < n ? latest : n - 1;
+                const uint64_t i = order_index(first, n), j = order_index(latest, n);  // (both rows' loads in flight)
                 if (!info[i].tombstone) flags |= HONU_SEEK_FIRST_LIVE;
                 if (!info[j].tombstone) flags |= HONU_SEEK_LATEST_LIVE;
             }
@@ -109,8 +100,6 @@ HONU_DEV void seek_finish(honu_seek *out, uint32_t pos, uint32_t end, uint32_t v
     }
     seek_store(out, pos, end, first, latest, flags);
 }
-
-HONU_DEV uint32_t seek_valid(const uint64_t *valid, uint64_t n) { return (uint32_t)(*valid < n ? *valid : n); }
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_seek_direct(
     const uint8_t *__restrict__ sorted, const uint64_t *__restrict__ valid, uint64_t n,
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_seek_direct(
         seek_store(out + q, 0, 0, HONU_SEEK_NONE, HONU_SEEK_NONE, HONU_SEEK_SKIPPED);
         return;
     }
-    const uint32_t v = seek_valid(valid, n);
+    const uint32_t v = (uint32_t)valid_rows(valid, n);
     uint32_t p[SORT_KEY_WORDS];
     load_masked(probes + HONU_KEY_LEN * q, M, p);
     uint32_t pos, end;
@@ -142,7 +131,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_seek_fenced(
     uint64_t m, const uint32_t *__restrict__ order, const honu_record_info *__restrict__ info,
     honu_seek *__restrict__ out) {
     __shared__ u32x4 fence[SEEK_FENCE][2];
-    const uint32_t v = seek_valid(valid, n);
+    const uint32_t v = (uint32_t)valid_rows(valid, n);
     const bool sampled = v > SEEK_FENCE;
     const uint32_t fe = sampled ? SEEK_FENCE : v;
     auto at = [&](uint32_t i) -> uint32_t {

@@ -22,7 +22,7 @@
 // has more rows than the context's scan state is sized for), then a stable
 // scatter. No spin-wait of its own.
 #include "kernels.h"
-#include "keypack.h"
+#include "keycol.h"
 
 namespace honu {
 
@@ -36,7 +36,6 @@ constexpr int PLAN_FINAL = 30, PLAN_MASK = 32, PLAN_WORDS = 64;
 
 uint32_t sort_tile() { return SORT_TILE; }
 
-static uint64_t up256(uint64_t x) { return (x + 255) & ~255ull; }
 static uint64_t sort_tiles(uint64_t n) { return (n + SORT_TILE - 1) / SORT_TILE; }
 
 uint64_t sort_workspace_bytes(uint64_t n) {
@@ -237,24 +236,12 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_sort_emit(const uint8_t *__restr
     if (!sorted) return;
     uint8_t *out = sorted + HONU_KEY_LEN * p;
     if (!ok) {  // packed as zeros: the row's own bytes
-        const uint8_t *k = keys + (uint64_t)HONU_KEY_LEN * ix;
-        const u32x4 a = *reinterpret_cast<const u32x4u *>(k), b = *reinterpret_cast<const u32x4u *>(k + 13);
-        *reinterpret_cast<u32x4u *>(out) = a;
-        *reinterpret_cast<u32x4u *>(out + 13) = b;
+        copy_key(out, keys + (uint64_t)HONU_KEY_LEN * ix);
         return;
     }
     const u32x4 k1 = key[2 * p + 1];
     const uint32_t w[SORT_KEY_WORDS] = {k0.x, k0.y, k0.z, k0.w, k1.x, k1.y, k1.z, k1.w};
-    // key bytes [0,16) and [13,29) as little-endian words: key byte j is packed byte j + 1
-    uint32_t a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int pa = j + 1, pb = j + 14;
-        a[j >> 2] |= ((w[pa >> 2] >> (8 * (3 - (pa & 3)))) & 0xFFu) << (8 * (j & 3));
-        b[j >> 2] |= ((w[pb >> 2] >> (8 * (3 - (pb & 3)))) & 0xFFu) << (8 * (j & 3));
-    }
-    *reinterpret_cast<u32x4u *>(out) = u32x4{a[0], a[1], a[2], a[3]};
-    *reinterpret_cast<u32x4u *>(out + 13) = u32x4{b[0], b[1], b[2], b[3]};
+    unpack_key(out, w);
 }
 
 hipError_t launch_sort_keys(const uint8_t *keys, const int32_t *status, uint64_t n, uint32_t *order,
@@ -293,8 +280,6 @@ HONU_DEV bool same_prefix(const uint8_t *x, const uint8_t *y) {
     return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w && x[16] == y[16];
 }
 
-HONU_DEV uint64_t clamp_valid(const uint64_t *valid, uint64_t n) { return *valid < n ? *valid : n; }
-
 // col[p] = 1 where position p starts an object (p < valid), else 0
 __global__ __launch_bounds__(HONU_BLOCK) void k_obj_heads(const uint8_t *__restrict__ keys,
                                                           const uint32_t *__restrict__ order,
@@ -303,10 +288,8 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_obj_heads(const uint8_t *__restr
     const uint64_t p = (uint64_t)blockIdx.x * HONU_BLOCK + threadIdx.x;
     if (p >= n) return;
     uint64_t head = 0;
-    if (p < clamp_valid(valid, n)) {
-        // (an index is below n in an order honu_sort_keys wrote; whatever else it holds reads row n - 1)
-        const uint64_t i = order[p] < n ? order[p] : n - 1;
-        const uint64_t j = p ? (order[p - 1] < n ? order[p - 1] : n - 1) : 0;
+    if (p < valid_rows(valid, n)) {
+        const uint64_t i = order_index(order[p], n), j = p ? order_index(order[p - 1], n) : 0;
         head = p == 0 || !same_prefix(keys + HONU_KEY_LEN * i, keys + HONU_KEY_LEN * j);
     }
     col[p] = head;
@@ -320,7 +303,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_obj_place(const uint32_t *__rest
                                                           uint64_t *__restrict__ obj_off,
                                                           uint32_t *__restrict__ latest) {
     const uint64_t p = (uint64_t)blockIdx.x * HONU_BLOCK + threadIdx.x;
-    const uint64_t v = clamp_valid(valid, n), total = *objects;
+    const uint64_t v = valid_rows(valid, n), total = *objects;
     if (p > v) return;
     if (p == v) {
         obj_off[total] = v;

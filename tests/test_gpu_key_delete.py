@@ -238,6 +238,21 @@ def test_sizes(codec, T, sn):
         assert removed == len({r.tobytes() for r in drawn}) and kept == n - removed
 
 
+@pytest.mark.parametrize("m", [4097, 4225])
+def test_range_search_over_a_long_list(codec, T, m):
+    """A delete list of m rows over a column of T + 1: each tile's two wave
+    searches run over the whole list, a bracket of more than 4096 rows (and,
+    at 4225, above the 4160 from which the search takes a third step). Half of
+    the delete rows are drawn from the column, half random."""
+    rng = np.random.default_rng(9100 + m)
+    n = T + 1
+    k = random_keys(n, rng)
+    drawn = k[rng.integers(0, n, m // 2)]
+    dk = np.concatenate([drawn, random_keys(m - len(drawn), rng)])
+    S, order, kept, removed = delete_and_check(codec, side_of(k), side_of(dk), phases=PHASES[m % len(PHASES)])
+    assert removed == len({r.tobytes() for r in drawn}) and kept == n - removed
+
+
 def test_nothing_removed(codec, T):
     rng = np.random.default_rng(81)
     col = side_of(random_keys(2 * T + 3, rng))

@@ -330,6 +330,22 @@ def test_run_of_empty_ranges(codec, T, S, empties):
     list_and_check(codec, S_, n, seek_rows([(1, T)] + run + [(0, T + 1)]), order=order)
 
 
+@pytest.mark.parametrize("m", [4097, 4225])
+def test_tile_ends_searched_over_a_long_list(codec, T, m):
+    """m ranges, all empty but every 64th (40 rows each): some 2600 output rows
+    in three tiles, each tile's two wave searches over all m offsets, a bracket
+    of more than 4096 (and, at 4225, above the 4160 from which the search
+    takes a third step)."""
+    n = 2 * T
+    S_, order, tomb = column(n, 6)
+    empty = [(5, 5), (9, 3), (n + 4, n + 9)]
+    pairs = [(7 * i % (n - 40), 7 * i % (n - 40) + 40) if i % 64 == 1 else empty[i % 3] for i in range(m)]
+    for flags, ph in ((0, PHASES[1]), (LIST_REVERSE, PHASES[2])):
+        rows, off, _ = list_and_check(codec, S_, n, seek_rows(pairs), flags=flags, phases=ph, order=order, tomb=tomb)
+        assert len(rows) == 40 * len(range(1, m, 64)) > 2 * T and off[-1] == len(rows)
+        assert (rows["flags"] & LIST_ROW_HEAD).sum() == len(range(1, m, 64))
+
+
 def test_overlapping_repeated_out_of_order_and_clamped(codec, T):
     n = T + 77
     S_, order, tomb = column(n, 5)

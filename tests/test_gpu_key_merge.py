@@ -215,6 +215,19 @@ def test_sizes(codec, T, sa):
         assert valid == na + nb and sorted(order.tolist()) == list(range(na + nb))
 
 
+@pytest.mark.parametrize("na,nb", [(4097, 63), (6000, 6000)])
+def test_split_over_a_long_bracket(codec, T, na, nb):
+    """The tile's split is a wave search over the bracket [max(d - nb, 0),
+    min(d, na)) of a diagonal d. 4097 rows against 63: a long column beside a
+    short one, the bracket never above 63 rows. 6000 against 6000: the diagonal
+    5 T = 5120 has the bracket [0, 5120), above the 4160 rows from which the
+    search takes a third step (64 mids a step: a bracket of s > 64 rows leaves
+    at most ceil(s / 64) - 1)."""
+    rng = np.random.default_rng(7100 + na)
+    S, order, valid = merge_of_columns(codec, random_keys(na, rng), None, random_keys(nb, rng), None, phases=PHASES[1])
+    assert valid == na + nb and sorted(order.tolist()) == list(range(na + nb))
+
+
 def test_diagonal_extremes(codec, T):
     """Every A key below every B key, then every B key below every A key."""
     rng = np.random.default_rng(61)
