@@ -914,9 +914,9 @@ func (r ListRow) Tombstone() bool { return r.Flags&C.HONU_LIST_ROW_TOMBSTONE != 
 // (the keys that share an ObjectPrefix, keys.go:74-79) is visited. offsets[q]
 // is where range q's rows start in rows and offsets[len(seeks)] their number.
 // info (the decode's record info rows on the device, or a zero devBuf) sets
-// Tombstone; tombstones are flagged, not filtered (collection.go:132-134), and
-// the record values are not gathered. The first call counts, the second emits:
-// the total is the one host round trip.
+// Tombstone; tombstones are flagged, not filtered (collection.go:132-134); the
+// record values of the rows are FetchObjects'. The first call counts, the
+// second emits: the total is the one host round trip.
 //
 // UNCOMPILED, like the rest of this file. honu_key_list is exercised on the
 // GPU from Python (tests/test_gpu_key_list.py), graph capture included.
@@ -996,6 +996,91 @@ func (c *Codec) ListKeys(o *KeyOrder, seeks []Seek, limit uint32, reverse, lates
 		rows[g] = ListRow{uint32(r._range), uint32(r.pos), uint32(r.record), uint32(r.flags)}
 	}
 	return rows, offsets, nil
+}
+
+// FetchObjects is Cursor.Object() (iterator/cursor.go:31-38: make + copy of
+// the value under the cursor) for the rows of ListKeys: the step List, Versions
+// and Retrieve (collection.go:32-35, 97-110) end in. rec, recOff (nrec + 1
+// offsets) and recBytes are the records arena on the device; values[g] is the
+// record rows[g] names, nil where its index or offsets are out of range
+// (HONU_ERR_INPUT) and, with live, where the row is a tombstone (the object a
+// listing does not return, collection.go:132-134; the row stays in place). The
+// first call sizes (val_cap 0), the second copies: the byte total is the one
+// host round trip. A caller that decodes on the device keeps dValues and
+// dValOff there instead: they are the arena and offsets of honu_decode_batch.
+//
+// UNCOMPILED, like the rest of this file. honu_key_fetch is exercised on the
+// GPU from Python (tests/test_gpu_key_fetch.py), graph capture included.
+func (c *Codec) FetchObjects(rows []ListRow, rec, recOff devBuf, nrec, recBytes uint64, live bool) (values [][]byte, err error) {
+	w := uint64(len(rows))
+	if w == 0 {
+		return nil, nil
+	}
+	rowSize := uint64(C.honu_sizeof_list_row())
+	hRows, hOff, hStatus, hTotal := pinned(uintptr(rowSize*w)), pinned(uintptr(8*(w+1))), pinned(uintptr(4*w)), pinned(8)
+	defer hRows.free()
+	defer hOff.free()
+	defer hStatus.free()
+	defer hTotal.free()
+	in := unsafe.Slice((*C.honu_list_row)(hRows.p), w)
+	for g, r := range rows {
+		in[g]._range, in[g].pos, in[g].record, in[g].flags = C.uint32_t(r.Range), C.uint32_t(r.Pos), C.uint32_t(r.Record), C.uint32_t(r.Flags)
+	}
+	*(*uint64)(hTotal.p) = w
+	dRows, dTotal, dOff, dStatus, dNeed := device(hRows.n), device(8), device(hOff.n), device(hStatus.n), device(8)
+	defer dRows.free()
+	defer dTotal.free()
+	defer dOff.free()
+	defer dStatus.free()
+	defer dNeed.free()
+	var flags C.uint32_t
+	if live {
+		flags |= C.HONU_FETCH_LIVE
+	}
+	fetch := func(dValues devBuf, valCap uint64) C.int32_t {
+		return C.honu_key_fetch(c.ctx, (*C.honu_list_row)(dRows.p), (*C.uint64_t)(dTotal.p), C.uint64_t(w),
+			(*C.uint8_t)(rec.p), (*C.uint64_t)(recOff.p), C.uint64_t(nrec), C.uint64_t(recBytes), flags,
+			(*C.uint64_t)(dOff.p), (*C.int32_t)(dStatus.p), (*C.uint8_t)(dValues.p), C.uint64_t(valCap),
+			(*C.uint64_t)(dNeed.p), c.stream)
+	}
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(dRows.p, hRows.p, C.uint64_t(hRows.n), c.stream),
+		C.honu_memcpy_h2d(dTotal.p, hTotal.p, 8, c.stream),
+		fetch(devBuf{}, 0), // sizes only
+		C.honu_memcpy_d2h(hOff.p, dOff.p, C.uint64_t(hOff.n), c.stream),
+		C.honu_memcpy_d2h(hStatus.p, dStatus.p, C.uint64_t(hStatus.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_fetch", s); err != nil {
+			return nil, err
+		}
+	}
+	off := unsafe.Slice((*uint64)(hOff.p), w+1)
+	status := unsafe.Slice((*int32)(hStatus.p), w)
+	values = make([][]byte, w)
+	need := off[w]
+	if need == 0 {
+		return values, nil
+	}
+	hValues, dValues := pinned(uintptr(need)), device(uintptr(need))
+	defer hValues.free()
+	defer dValues.free()
+	for _, s := range []C.int32_t{
+		fetch(dValues, need),
+		C.honu_memcpy_d2h(hValues.p, dValues.p, C.uint64_t(need), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_fetch", s); err != nil {
+			return nil, err
+		}
+	}
+	all := unsafe.Slice((*byte)(hValues.p), need)
+	for g := range values {
+		if status[g] == C.HONU_OK && !(live && rows[g].Tombstone()) {
+			values[g] = append([]byte{}, all[off[g]:off[g+1]]...) // Object()'s make + copy
+		}
+	}
+	return values, nil
 }
 
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&

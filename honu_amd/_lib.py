@@ -60,6 +60,7 @@ _PROTOS = {
     "honu_key_delete": (I32, [P, P, P, P, U64, P, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P, U64, P]),
     "honu_sizeof_list_row": (U64, []),
     "honu_key_list": (I32, [P, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P, P, U64, P, P]),
+    "honu_key_fetch": (I32, [P, P, P, U64, P, P, U64, U64, C.c_uint32, P, P, P, U64, P, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -890,6 +890,31 @@ int32_t honu_key_list(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_
 }
 
 // ---------------------------------------------------------------------------
+// Cursor.Object() over listed rows (iterator/cursor.go:31-38;
+// collection.go:32-35, 97-110)
+// ---------------------------------------------------------------------------
+int32_t honu_key_fetch(honu_ctx *ctx, const honu_list_row *d_rows, const uint64_t *d_total, uint64_t cap,
+                       const uint8_t *d_rec, const uint64_t *d_rec_off, uint64_t nrec, uint64_t rec_bytes,
+                       uint32_t flags, uint64_t *d_val_off, int32_t *d_status, uint8_t *d_values, uint64_t val_cap,
+                       uint64_t *d_val_total, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (cap > 0xFFFFFFFFull || nrec > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    // the cap + 1 lengths are scanned in place with the context's scan state, which covers max_records rows
+    if (cap + 1 > ctx->max_n) return HONU_E_WORKSPACE;
+    if (flags & ~(uint32_t)HONU_FETCH_LIVE) return arg_fail("unknown flag bits");
+    if (!d_total || !d_val_off || !d_val_total) return arg_fail("null d_total, d_val_off or d_val_total");
+    if ((cap && !d_rows) || !d_rec_off) return arg_fail("null rows or record offsets");
+    if ((rec_bytes && !d_rec) || (val_cap && !d_values)) return arg_fail("null arena of a size other than 0");
+    if (!aligned(d_status, 4) || !aligned(d_total, 8) || !aligned(d_rec_off, 8) || !aligned(d_val_off, 8) ||
+        !aligned(d_val_total, 8) || !aligned(d_rows, 16))
+        return arg_fail("status 4-byte / counts and offsets 8-byte / rows 16-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_fetch(copy_geom(ctx), d_rows, d_total, cap, d_rec, d_rec_off, nrec, rec_bytes, flags,
+                            d_val_off, d_status, d_values, val_cap, d_val_total, ctx->scan, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
 // system objects (object/system.go)
 // ---------------------------------------------------------------------------
 int32_t honu_system_sizes(honu_ctx *ctx, const honu_collection *d_rows, uint64_t var_len,

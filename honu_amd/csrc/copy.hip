@@ -100,6 +100,38 @@ struct SpanSegments {
     }
 };
 
+// Segment g of honu_key_fetch (fetch.hip): row g of a list, logical start =
+// val_off[g] (the destination offset, the scanned lengths: n + 1 values, flat
+// from the list's last row on), src = rec + rec_off[rows[g].record].
+// The length is the difference of the scanned offsets, and it is the validity
+// too: the length pass gave a row a length other than 0 only after it found
+// the record index below nrec and the offsets in order inside the arena, so a
+// row with a length needs no second check, and a row without one (past the
+// list's end, a tombstone left out, a refused index or offset pair) is not
+// looked up in rec_off at all.
+struct FetchSegments {
+    const honu_list_row *rows;
+    const uint8_t *rec;
+    const uint64_t *rec_off;
+    const uint64_t *val_off;
+    uint8_t *values;
+    uint64_t val_cap;
+
+    HONU_DEV uint64_t start(uint64_t g) const { return val_off[g]; }
+    HONU_DEV uint64_t lo() const { return 0; }
+    HONU_DEV bool get(uint64_t g, uint64_t &len, const uint8_t *&src, uint8_t *&dst, uint64_t &skip) const {
+        skip = 0;
+        const uint64_t o0 = val_off[g], o1 = val_off[g + 1];  // with the row's index in one round trip
+        const uint32_t r = rows[g].record;
+        len = o1 - o0;
+        // the rows that fit are a prefix (the offsets are monotone); nothing is written at or past val_cap
+        const bool ok = len != 0 && o1 <= val_cap;
+        src = rec + (ok ? rec_off[r] : 0);
+        dst = values + o0;
+        return ok;
+    }
+};
+
 #define SMALL_SEG_WAVES_FACTOR 4
 // average segment bytes from which a launch uses 1 / SMALL_SEG_WAVES_FACTOR of
 // its waves
@@ -302,6 +334,17 @@ hipError_t launch_decode_copy(const LaunchGeom &g, const uint8_t *rec, uint64_t 
     if (n == 0) return hipSuccess;
     DecodeSegments seg{rec, info, scratch, offs, data, n};  // (n: the unread n_)
     return launch_copy(g, seg, n, totals + 2, g.copy_tickets, s);
+}
+
+// n = the list's cap: segments [0, n), the total at val_off + n. The full grid
+// however few rows the list holds, and the classes by total / n, not by the
+// rows listed: both counts are on the device only
+hipError_t launch_fetch_copy(const LaunchGeom &g, const honu_list_row *rows, uint64_t n, const uint8_t *rec,
+                             const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
+                             uint64_t val_cap, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    FetchSegments seg{rows, rec, rec_off, val_off, values, val_cap};
+    return launch_copy(g, seg, n, val_off + n, g.copy_tickets, s);
 }
 
 }  // namespace honu

@@ -303,6 +303,19 @@ hipError_t launch_key_list(int num_cu, const uint8_t *sorted, const uint32_t *or
                            uint64_t *range_off, honu_list_row *rows, uint8_t *keys_out, uint64_t cap,
                            uint64_t *total, const ScanState &S, hipStream_t s);
 
+// fetch.hip: Cursor.Object() (iterator/cursor.go:31-38) for the rows of a list: the records they name,
+// packed into a CSR arena (val_off: cap + 1 values, the lengths scanned in place through launch_scan, so
+// cap + 1 must not exceed the rows the context's scan state covers). cap, nrec <= 2^32 - 1. No workspace.
+// g: the call's own copy geometry (api.hip copy_geom). The copy itself is launch_fetch_copy (copy.hip),
+// FetchSegments over the byte-balanced engine
+hipError_t launch_key_fetch(const LaunchGeom &g, const honu_list_row *rows, const uint64_t *total, uint64_t cap,
+                            const uint8_t *rec, const uint64_t *rec_off, uint64_t nrec, uint64_t rec_bytes,
+                            uint32_t flags, uint64_t *val_off, int32_t *status, uint8_t *values, uint64_t val_cap,
+                            uint64_t *val_total, const ScanState &S, hipStream_t s);
+hipError_t launch_fetch_copy(const LaunchGeom &g, const honu_list_row *rows, uint64_t n, const uint8_t *rec,
+                             const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
+                             uint64_t val_cap, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

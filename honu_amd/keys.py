@@ -21,6 +21,9 @@ every read path, the walk with Cursor.Next() or Cursor.Prev()
 (iterator/cursor.go:57-89) that List, Versions and Retrieve
 (collection.go:32-35, 97-110) and the loop of store.go:379 are made of, over a
 batch of seek() ranges; the batch form is Codec.list_keys (honu_key_list).
+fetch() is the host statement of what every one of those walks does at each
+row, Cursor.Object() (iterator/cursor.go:31-38), over scan()'s list; the batch
+form is Codec.fetch_objects (honu_key_fetch).
 """
 from __future__ import annotations
 
@@ -225,6 +228,30 @@ def scan(sorted_keys: Sequence[bytes], ranges: Iterable, reverse: bool = False, 
         else:
             walk = list(walk)
         out.extend((q, p) for p in (walk[:limit] if limit else walk))
+    return out
+
+
+def fetch(values: Sequence[bytes], visits: Iterable, order: Sequence[int], live=None):
+    """Cursor.Object() (iterator/cursor.go:31-38: `obj := make([]byte,
+    len(c.value)); copy(obj, c.value)`) at every row of a walk: for scan()'s
+    list of (range, pos) the list of values[order[pos]], each a copy, in the
+    walk's order. `order` maps a position of the sorted list to the index of
+    its record (sort_keys' order), `values` holds the records. An index that
+    is out of range, of `order` or of `values`, gives None, as Object() gives
+    nil for a cursor without a value. `live`, when given, is a predicate on
+    the record index that says False for a tombstone: such a row gives None
+    too and stays in the list, the object that "will not be returned in list
+    queries" (collection.go:132-134). A record named by several rows
+    (overlapping ranges) is returned once per row. The batch form on the GPU
+    is Codec.fetch_objects (honu_key_fetch in include/honu_codec.h)."""
+    out = []
+    for _, pos in visits:
+        pos = int(pos)
+        r = int(order[pos]) if 0 <= pos < len(order) else -1
+        if not 0 <= r < len(values) or (live is not None and not live(r)):
+            out.append(None)
+        else:
+            out.append(bytes(values[r]))
     return out
 
 

@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, INFO_DTYPE, LIST_LATEST, LIST_REVERSE, META_DTYPE, HostBatch,
-                       Metadata, pack_batch, unpack_row)
+from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, FETCH_LIVE, INFO_DTYPE, LIST_LATEST, LIST_REVERSE, META_DTYPE,
+                       HostBatch, Metadata, pack_batch, unpack_row)
 
 StorageVersion = 1  # object.go:14
 
@@ -422,6 +422,32 @@ class Codec:
         torch = _torch()
         return (rows[:16 * cap].view(torch.int32).view(cap, 4), range_off[:8 * (m + 1)].view(torch.int64),
                 total[:8].view(torch.int64), keys[:29 * cap] if want_keys else None)
+
+    def fetch_objects(self, rows, total, cap: int, rec, rec_off, nrec: int, rec_bytes: int, val_cap: int,
+                      live: bool = False):
+        """Cursor.Object() (iterator/cursor.go:31-38: make + copy of the value
+        under the cursor) for the rows of list_keys, which stay on the device
+        with their total: the records they name, out of the CSR arena (rec,
+        rec_off uint64[nrec + 1], rec_bytes readable bytes), packed into a CSR
+        arena of val_cap bytes. Returns (values: uint8[val_cap]; val_off:
+        int64[cap + 1], where each row's value starts and the bytes they all
+        need; val_total: one int64, the same need; status: int32[cap], of
+        which min(total, cap) are written, INPUT for a row whose record index
+        or offsets are out of range), all on the device: the (rec, rec_off,
+        n = cap) of Codec.decode. The rows with val_off[g + 1] <= val_cap are
+        copied, a prefix; a caller that reads val_total > val_cap calls again
+        with more room (val_cap 0 only sizes). With `live`, a row flagged
+        LIST_ROW_TOMBSTONE fetches nothing and stays in place, an empty
+        value."""
+        values = self._empty(val_cap) if val_cap else None
+        val_off, val_total, status = self._empty(8 * (cap + 1)), self._empty(8), self._empty(4 * cap)
+        _lib.check(self.lib.honu_key_fetch(
+            self.ctx, _lib.ptr(rows), _lib.ptr(total), cap, _lib.ptr(rec), _lib.ptr(rec_off), nrec, rec_bytes,
+            FETCH_LIVE if live else 0, _lib.ptr(val_off), _lib.ptr(status), _lib.ptr(values), val_cap,
+            _lib.ptr(val_total), self.stream), "honu_key_fetch")
+        torch = _torch()
+        return (values[:val_cap] if val_cap else None, val_off[:8 * (cap + 1)].view(torch.int64),
+                val_total[:8].view(torch.int64), status[:4 * cap].view(torch.int32))
 
 
 _default: Optional[Codec] = None

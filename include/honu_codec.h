@@ -22,6 +22,7 @@
  *   bucket.Put (a batch)        store.go:232, 395, 530 honu_key_merge (stable merge into the sorted column)
  *   bucket.Delete (a batch)     store.go:378-383, 399-404 honu_key_delete (stable compaction of the sorted column)
  *   Cursor.Next / Prev (batch)  iterator/cursor.go:57-89  honu_key_list (the rows of a batch of seek ranges, packed)
+ *   Cursor.Object() (batch)     iterator/cursor.go:31-38  honu_key_fetch (the records the listed rows name, a CSR arena)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -818,8 +819,9 @@ uint64_t honu_sizeof_list_row(void);
  * Tombstones. Collection.Delete's comment says an object with a tombstone
  * version "will not be returned in list queries" (collection.go:132-134).
  * Here a tombstone is FLAGGED (HONU_LIST_ROW_TOMBSTONE, when d_info is
- * given), not filtered: the filter is not built, and neither is a gather of
- * the record values themselves.
+ * given), not filtered: the filter, a compaction of the rows, is not built
+ * (honu_key_fetch with HONU_FETCH_LIVE fetches nothing for a flagged row and
+ * leaves the row in place).
  * Outputs. d_range_off[0, m] is the exclusive scan of the c_q and
  * d_range_off[m] = d_total[0] = total, a 64-bit sum (overlapping ranges can
  * exceed n). w = min(total, cap): only output rows g < w are written. Row g
@@ -858,6 +860,67 @@ int32_t honu_key_list(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *d_
                       const honu_record_info *d_info,
                       uint64_t *d_range_off, honu_list_row *d_rows, uint8_t *d_keys_out,
                       uint64_t cap, uint64_t *d_total, void *stream);
+
+/* honu_key_fetch flags */
+enum {
+    HONU_FETCH_LIVE = 1u << 0 /* rows flagged HONU_LIST_ROW_TOMBSTONE fetch nothing */
+};
+
+/* Cursor.Object() over listed rows: the step every reference read path ends
+ * in. Object() (iterator/cursor.go:31-38) is make + copy of the value under
+ * the cursor, once per row that List, Versions or Retrieve visits
+ * (collection.go:32-35, 97-110). For the rows honu_key_list wrote, the call
+ * copies the record each row names out of a CSR records arena into a packed
+ * CSR arena of its own (d_values, d_val_off): the input form of
+ * honu_decode_batch, honu_decode_headers and honu_decode_data, so seek, list,
+ * fetch and decode run on one stream with nothing read on the host. Every
+ * count stays on the device.
+ * Inputs. d_rows, d_total and cap are what honu_key_list wrote and was given:
+ * w = min(d_total[0], cap) is read on the device and only rows g < w take
+ * part. d_rec, d_rec_off[nrec + 1] are the records arena (any byte
+ * alignment), rec_bytes its readable size.
+ * Lengths. Row g < w names r = d_rows[g].record. With HONU_FETCH_LIVE and
+ * HONU_LIST_ROW_TOMBSTONE in d_rows[g].flags its length is 0 and its status
+ * HONU_OK, whatever r is, and d_rec_off is not read: Object() returning nil
+ * for the object that a listing does not return (collection.go:132-134). The
+ * row stays in place; compacting it away is not built. Otherwise r >= nrec
+ * (HONU_SEEK_NONE of a list made without d_order included) gives length 0 and
+ * HONU_ERR_INPUT; otherwise a = d_rec_off[r], b = d_rec_off[r + 1] give length
+ * b - a and HONU_OK when a <= b <= rec_bytes, else length 0 and
+ * HONU_ERR_INPUT. Rows g >= w have length 0 and no status. Rows may repeat a
+ * record (overlapping ranges do): its bytes are then read twice.
+ * Outputs. d_val_off[0, cap] is the exclusive scan of the lengths, packed with
+ * no padding, and d_val_off[cap] = d_val_total[0] the bytes the rows need.
+ * Row g is copied to d_values + d_val_off[g] exactly when its length is not 0
+ * and d_val_off[g + 1] <= val_cap; the offsets are monotone, so the copied
+ * rows are a prefix. A caller that reads d_val_total[0] > val_cap re-issues
+ * with more room, as with the list's cap: a prefix rule, not a status per row.
+ * The write set is exactly d_val_off[0, cap + 1), d_val_total[0],
+ * d_status[0, w) (d_status may be NULL) and the bytes of the copied rows in
+ * d_values. With cap == 0 only d_val_off[0] = 0 and d_val_total[0] = 0 are
+ * written. d_values may be NULL only with val_cap == 0: a sizing call.
+ * Asynchronous on `stream`, no host synchronisation, no allocation, no
+ * workspace beyond the outputs; replays from a captured graph, also after
+ * d_total and the rows were changed on the device between replays. The
+ * lengths are scanned in place in d_val_off by the context's scan, so one
+ * context serves one stream at a time, as for honu_key_list; the copy takes a
+ * line of the context's copy counters like every payload copy. Garbage in
+ * d_rows or d_rec_off may give wrong bytes, never a read of d_rec_off outside
+ * [0, nrec], a read of a record byte outside [0, rec_bytes) or a write outside
+ * the write set (the copy loads whole aligned 16-byte blocks that hold at
+ * least one byte of a record it copies, as every payload copy does).
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for cap or nrec above
+ * 2^32 - 1, or for cap + 1 above honu_ctx_max_records; HONU_E_ARG for a NULL
+ * ctx, d_total, d_val_off or d_val_total, a NULL d_rows with cap > 0, a NULL
+ * d_rec_off, a NULL d_rec with rec_bytes > 0, a NULL d_values with val_cap >
+ * 0, unknown flag bits, or a misaligned pointer (4 bytes: d_status; 8 bytes:
+ * d_total, d_rec_off, d_val_off, d_val_total; 16 bytes: d_rows). */
+int32_t honu_key_fetch(honu_ctx *ctx, const honu_list_row *d_rows, const uint64_t *d_total,
+                       uint64_t cap,
+                       const uint8_t *d_rec, const uint64_t *d_rec_off, uint64_t nrec,
+                       uint64_t rec_bytes, uint32_t flags,
+                       uint64_t *d_val_off, int32_t *d_status,
+                       uint8_t *d_values, uint64_t val_cap, uint64_t *d_val_total, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
