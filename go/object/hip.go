@@ -914,8 +914,8 @@ func (r ListRow) Tombstone() bool { return r.Flags&C.HONU_LIST_ROW_TOMBSTONE != 
 // (the keys that share an ObjectPrefix, keys.go:74-79) is visited. offsets[q]
 // is where range q's rows start in rows and offsets[len(seeks)] their number.
 // info (the decode's record info rows on the device, or a zero devBuf) sets
-// Tombstone; tombstones are flagged, not filtered (collection.go:132-134); the
-// record values of the rows are FetchObjects'. The first call counts, the
+// Tombstone; tombstones are flagged here and filtered by FilterRows
+// (collection.go:132-134); the record values of the rows are FetchObjects'. The first call counts, the
 // second emits: the total is the one host round trip.
 //
 // UNCOMPILED, like the rest of this file. honu_key_list is exercised on the
@@ -1081,6 +1081,92 @@ func (c *Codec) FetchObjects(rows []ListRow, rec, recOff devBuf, nrec, recBytes 
 		}
 	}
 	return values, nil
+}
+
+// FilterRows is what a listing leaves out: an object deleted with a tombstone
+// version "will not be returned in list queries or retrieval"
+// (collection.go:132-134), and Retrieve of it is "not found"
+// (collection.go:97-101). rows and offsets are ListKeys'; the rows that stay
+// come back in order, with offsets[q] where range q's kept rows start,
+// offsets[len(offsets)-1] their number and Head on the first kept row of each
+// range, so they pass to FetchObjects as they are: an empty range is "not
+// found". With tombstones a row whose Tombstone is set goes (the list was made
+// with info): right for lists of latest versions. With deleted every row of an
+// object whose latest version is a tombstone goes, wherever that version lies,
+// and an older tombstone version of a live object stays (Versions "includes
+// tombstone versions", collection.go:106-107); it needs info, the decode's
+// record info rows on the device, and an order that SortKeys returned.
+//
+// UNCOMPILED, like the rest of this file. honu_key_filter is exercised on the
+// GPU from Python (tests/test_gpu_key_filter.py), graph capture included.
+func (c *Codec) FilterRows(o *KeyOrder, rows []ListRow, offsets []uint64, tombstones, deleted bool, info devBuf) (kept []ListRow, keptOffsets []uint64, err error) {
+	w, m := uint64(len(rows)), uint64(len(offsets))-1
+	n := o.n
+	if w == 0 {
+		return nil, make([]uint64, m+1), nil
+	}
+	rowSize := uint64(C.honu_sizeof_list_row())
+	hRows, hOff, hTotal := pinned(uintptr(rowSize*w)), pinned(uintptr(8*(m+1))), pinned(8)
+	defer hRows.free()
+	defer hOff.free()
+	defer hTotal.free()
+	in := unsafe.Slice((*C.honu_list_row)(hRows.p), w)
+	for g, r := range rows {
+		in[g]._range, in[g].pos, in[g].record, in[g].flags = C.uint32_t(r.Range), C.uint32_t(r.Pos), C.uint32_t(r.Record), C.uint32_t(r.Flags)
+	}
+	copy(unsafe.Slice((*uint64)(hOff.p), m+1), offsets)
+	*(*uint64)(hTotal.p) = w
+	workBytes := uint64(C.honu_key_filter_workspace(C.uint64_t(w)))
+	dRows, dOff, dTotal := device(hRows.n), device(hOff.n), device(8)
+	dRowsOut, dOffOut, dTotalOut, work := device(hRows.n), device(hOff.n), device(8), device(uintptr(workBytes))
+	for _, b := range []devBuf{dRows, dOff, dTotal, dRowsOut, dOffOut, dTotalOut, work} {
+		defer b.free()
+	}
+	var flags C.uint32_t
+	if tombstones {
+		flags |= C.HONU_FILTER_TOMBSTONE
+	}
+	var dObjOff, dLatest, dObjects devBuf
+	if deleted {
+		if o.keys.p == nil || info.p == nil {
+			return nil, nil, fmt.Errorf("deleted needs an order that SortKeys returned and the record info")
+		}
+		flags |= C.HONU_FILTER_DELETED
+		sortBytes := uint64(C.honu_sort_keys_workspace(C.uint64_t(n)))
+		sortWork := device(uintptr(sortBytes))
+		dObjOff, dLatest, dObjects = device(uintptr(8*(n+1))), device(uintptr(4*n)), device(8)
+		for _, b := range []devBuf{sortWork, dObjOff, dLatest, dObjects} {
+			defer b.free()
+		}
+		if err = call("honu_key_objects", C.honu_key_objects(c.ctx, (*C.uint8_t)(o.keys.p), (*C.uint32_t)(o.order.p),
+			(*C.uint64_t)(o.valid.p), C.uint64_t(n), (*C.uint64_t)(dObjOff.p), (*C.uint32_t)(dLatest.p),
+			(*C.uint64_t)(dObjects.p), sortWork.p, C.uint64_t(sortBytes), c.stream)); err != nil {
+			return nil, nil, err
+		}
+	}
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(dRows.p, hRows.p, C.uint64_t(hRows.n), c.stream),
+		C.honu_memcpy_h2d(dOff.p, hOff.p, C.uint64_t(hOff.n), c.stream),
+		C.honu_memcpy_h2d(dTotal.p, hTotal.p, 8, c.stream),
+		C.honu_key_filter(c.ctx, (*C.honu_list_row)(dRows.p), nil, (*C.uint64_t)(dOff.p), C.uint64_t(m),
+			(*C.uint64_t)(dTotal.p), C.uint64_t(w), flags, (*C.uint64_t)(o.valid.p), C.uint64_t(n),
+			(*C.uint64_t)(dObjOff.p), (*C.uint32_t)(dLatest.p), (*C.uint64_t)(dObjects.p),
+			(*C.honu_record_info)(info.p), (*C.honu_list_row)(dRowsOut.p), nil, (*C.uint64_t)(dOffOut.p),
+			(*C.uint64_t)(dTotalOut.p), work.p, C.uint64_t(workBytes), c.stream),
+		C.honu_memcpy_d2h(hRows.p, dRowsOut.p, C.uint64_t(hRows.n), c.stream),
+		C.honu_memcpy_d2h(hOff.p, dOffOut.p, C.uint64_t(hOff.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_filter", s); err != nil {
+			return nil, nil, err
+		}
+	}
+	keptOffsets = append([]uint64(nil), unsafe.Slice((*uint64)(hOff.p), m+1)...)
+	kept = make([]ListRow, keptOffsets[m])
+	for g, r := range unsafe.Slice((*C.honu_list_row)(hRows.p), keptOffsets[m]) {
+		kept[g] = ListRow{uint32(r._range), uint32(r.pos), uint32(r.record), uint32(r.flags)}
+	}
+	return kept, keptOffsets, nil
 }
 
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&

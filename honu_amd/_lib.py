@@ -61,6 +61,8 @@ _PROTOS = {
     "honu_sizeof_list_row": (U64, []),
     "honu_key_list": (I32, [P, P, P, P, U64, P, U64, C.c_uint32, C.c_uint32, P, P, P, P, P, P, U64, P, P]),
     "honu_key_fetch": (I32, [P, P, P, U64, P, P, U64, U64, C.c_uint32, P, P, P, U64, P, P]),
+    "honu_key_filter_workspace": (U64, [U64]),
+    "honu_key_filter": (I32, [P, P, P, P, U64, P, U64, C.c_uint32, P, U64, P, P, P, P, P, P, P, P, P, U64, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

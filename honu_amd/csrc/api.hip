@@ -369,6 +369,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "delete_tile")) *value = delete_tile();  // read only: column positions per workgroup of the delete
     else if (!strcmp(name, "list_tile")) *value = list_tile();    // read only: output rows per workgroup of the list
     else if (!strcmp(name, "list_stage")) *value = list_stage();  // read only: range offsets a workgroup of the list stages in LDS
+    else if (!strcmp(name, "filter_tile")) *value = filter_tile();  // read only: list rows per workgroup of the filter
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -911,6 +912,46 @@ int32_t honu_key_fetch(honu_ctx *ctx, const honu_list_row *d_rows, const uint64_
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_fetch(copy_geom(ctx), d_rows, d_total, cap, d_rec, d_rec_off, nrec, rec_bytes, flags,
                             d_val_off, d_status, d_values, val_cap, d_val_total, ctx->scan, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the live-object filter over listed rows (collection.go:132-134, 97-101,
+// 53-54)
+// ---------------------------------------------------------------------------
+uint64_t honu_key_filter_workspace(uint64_t cap) { return filter_workspace_bytes(cap); }
+
+int32_t honu_key_filter(honu_ctx *ctx, const honu_list_row *d_rows, const uint8_t *d_keys,
+                        const uint64_t *d_range_off, uint64_t m, const uint64_t *d_total, uint64_t cap,
+                        uint32_t flags, const uint64_t *d_valid, uint64_t n, const uint64_t *d_obj_off,
+                        const uint32_t *d_latest, const uint64_t *d_objects, const honu_record_info *d_info,
+                        honu_list_row *d_rows_out, uint8_t *d_keys_out, uint64_t *d_range_off_out,
+                        uint64_t *d_total_out, void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (cap > 0xFFFFFFFFull || m > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    // the tiles' kept counts are scanned with the context's scan state, which covers max_records rows
+    if (filter_tiles(cap) > ctx->max_n) return HONU_E_WORKSPACE;
+    if (flags & ~(uint32_t)(HONU_FILTER_TOMBSTONE | HONU_FILTER_DELETED)) return arg_fail("unknown flag bits");
+    if (!d_range_off || !d_total || !d_range_off_out || !d_total_out)
+        return arg_fail("null d_range_off, d_total, d_range_off_out or d_total_out");
+    if (cap && (!d_rows || !d_rows_out)) return arg_fail("null rows");
+    if ((flags & HONU_FILTER_DELETED) && (!d_valid || !d_obj_off || !d_latest || !d_objects || !d_info))
+        return arg_fail("DELETED needs d_valid, d_obj_off, d_latest, d_objects and d_info");
+    if (!d_keys != !d_keys_out) return arg_fail("d_keys and d_keys_out go together");
+    if ((d_rows && d_rows_out == d_rows) || d_range_off_out == d_range_off || d_total_out == d_total ||
+        (d_keys && d_keys_out == d_keys))
+        return arg_fail("an output is an input");
+    if (!aligned(d_latest, 4) || !aligned(d_range_off, 8) || !aligned(d_total, 8) || !aligned(d_valid, 8) ||
+        !aligned(d_obj_off, 8) || !aligned(d_objects, 8) || !aligned(d_info, 8) || !aligned(d_range_off_out, 8) ||
+        !aligned(d_total_out, 8) || !aligned(d_rows, 16) || !aligned(d_rows_out, 16))
+        return arg_fail("latest 4-byte / counts, offsets and info 8-byte / rows 16-byte aligned");
+    const uint64_t need = filter_workspace_bytes(cap);
+    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_filter_workspace(cap)");
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_filter(d_rows, d_keys, d_range_off, m, d_total, cap, flags, d_valid, n, d_obj_off, d_latest,
+                             d_objects, d_info, d_rows_out, d_keys_out, d_range_off_out, d_total_out, d_work,
+                             ctx->scan, (hipStream_t)stream));
     return HONU_OK;
 }
 

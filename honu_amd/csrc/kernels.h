@@ -316,6 +316,21 @@ hipError_t launch_fetch_copy(const LaunchGeom &g, const honu_list_row *rows, uin
                              const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
                              uint64_t val_cap, hipStream_t s);
 
+// filter.hip: the live-object filter (collection.go:132-134) over the rows of a list: a stable compaction
+// of the rows (and their keys) that stay, the ranges' offsets and HEAD flags recomputed. m, cap, n <=
+// 2^32 - 1. The workspace is the caller's (filter_workspace_bytes(cap)). The tiles' counts go through
+// launch_scan: filter_tiles(cap) must not exceed the rows the context's scan state covers (its max_records).
+// The column's arrays (valid .. info) are read with HONU_FILTER_DELETED only
+uint32_t filter_tile();
+uint64_t filter_tiles(uint64_t cap);
+uint64_t filter_workspace_bytes(uint64_t cap);
+hipError_t launch_key_filter(const honu_list_row *rows, const uint8_t *keys, const uint64_t *range_off, uint64_t m,
+                             const uint64_t *total, uint64_t cap, uint32_t flags, const uint64_t *valid, uint64_t n,
+                             const uint64_t *obj_off, const uint32_t *latest, const uint64_t *objects,
+                             const honu_record_info *info, honu_list_row *rows_out, uint8_t *keys_out,
+                             uint64_t *range_off_out, uint64_t *total_out, void *work, const ScanState &S,
+                             hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

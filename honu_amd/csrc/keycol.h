@@ -1,6 +1,6 @@
 // keycol.h — what the kernels over the ordered key column share: the sort
 // (sort.hip), the seek (seek.hip), the merge (merge.hip), the delete
-// (delete.hip) and the list (list.hip).
+// (delete.hip), the list (list.hip) and the filter (filter.hip).
 //   the packed key  a 29-byte key as 32 bytes read as eight big-endian words,
 //                   byte 0 the validity (0 valid, 1 not), bytes 1-29 the key,
 //                   bytes 30-31 zero. An unsigned compare of the words from

@@ -23,7 +23,10 @@ every read path, the walk with Cursor.Next() or Cursor.Prev()
 batch of seek() ranges; the batch form is Codec.list_keys (honu_key_list).
 fetch() is the host statement of what every one of those walks does at each
 row, Cursor.Object() (iterator/cursor.go:31-38), over scan()'s list; the batch
-form is Codec.fetch_objects (honu_key_fetch).
+form is Codec.fetch_objects (honu_key_fetch). filter() is the host statement
+of what a listing leaves out, the object deleted with a tombstone version that
+"will not be returned in list queries or retrieval" (collection.go:132-134),
+over scan()'s list; the batch form is Codec.filter_rows (honu_key_filter).
 """
 from __future__ import annotations
 
@@ -214,8 +217,9 @@ def scan(sorted_keys: Sequence[bytes], ranges: Iterable, reverse: bool = False, 
     (ObjectPrefix, keys.go:74-79), so an object whose latest version lies
     outside the range is not visited. pos and end are clamped to the list
     (end to its length, pos to end); ranges may be empty, overlap, repeat and
-    come in any order. Tombstones are not filtered. The batch form on the GPU
-    is Codec.list_keys (honu_key_list in include/honu_codec.h)."""
+    come in any order. Tombstones are not filtered here: filter() does. The
+    batch form on the GPU is Codec.list_keys (honu_key_list in
+    include/honu_codec.h)."""
     n = len(sorted_keys)
     out = []
     for q, (pos, end) in enumerate(ranges):
@@ -252,6 +256,42 @@ def fetch(values: Sequence[bytes], visits: Iterable, order: Sequence[int], live=
             out.append(None)
         else:
             out.append(bytes(values[r]))
+    return out
+
+
+def filter(sorted_keys: Sequence[bytes], visits: Iterable, tomb, order: Optional[Sequence[int]] = None,
+           deleted: bool = False):
+    """What a listing leaves out: an object deleted with a tombstone version
+    "will not be returned in list queries or retrieval"
+    (collection.go:132-134), and Retrieve of it is "not found"
+    (collection.go:97-101, 53-54). For scan()'s list of (range, pos) the
+    visits that stay, in the walk's order. `tomb` is a predicate on the record
+    index that says True for a tombstone; `order` maps a position of the
+    sorted list to the index of its record (sort_keys' order), None where the
+    position is the index. A visit goes when the record of its own row is a
+    tombstone: right for a walk over latest versions (scan(latest=True), or
+    reverse with limit 1 over object ranges). With `deleted` it goes when the
+    record of its object's latest row is one, the last row of the group of
+    keys with the same first 17 bytes (ObjectPrefix, keys.go:74-79), wherever
+    that row lies: every version of a deleted object goes, its live older
+    versions included, and a tombstone version of an object whose latest
+    version is live stays (Versions() "includes tombstone versions",
+    collection.go:106-107). A position outside the list, or outside `order`,
+    names no object and stays. A visit's fate does not depend on the other
+    visits, so both rules together are one call after the other. A range
+    with no visit left is Retrieve's "not found". The batch form on the GPU is
+    Codec.filter_rows (honu_key_filter in include/honu_codec.h)."""
+    n = len(sorted_keys)
+    out = []
+    for q, pos in visits:
+        p = int(pos)
+        if 0 <= p < n and deleted:  # the object's latest row
+            prefix = bytes(sorted_keys[p])[:PREFIX_SIZE]
+            while p + 1 < n and bytes(sorted_keys[p + 1])[:PREFIX_SIZE] == prefix:
+                p += 1
+        if 0 <= p < n and (order is None or p < len(order)) and tomb(p if order is None else int(order[p])):
+            continue
+        out.append((q, pos))
     return out
 
 

@@ -73,6 +73,8 @@ LIST_ROW_DTYPE = np.dtype(
 LIST_REVERSE, LIST_LATEST = 1 << 0, 1 << 1            # honu_key_list flags: Prev() from end - 1; one row per object
 LIST_ROW_HEAD, LIST_ROW_TOMBSTONE = 1 << 0, 1 << 1    # honu_list_row.flags
 FETCH_LIVE = 1 << 0  # honu_key_fetch flag (Codec.fetch_objects): rows flagged LIST_ROW_TOMBSTONE fetch nothing
+# honu_key_filter flags (Codec.filter_rows): drop rows flagged LIST_ROW_TOMBSTONE; drop every row of an object whose latest version is a tombstone
+FILTER_TOMBSTONE, FILTER_DELETED = 1 << 0, 1 << 1
 
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1

@@ -23,8 +23,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, FETCH_LIVE, INFO_DTYPE, LIST_LATEST, LIST_REVERSE, META_DTYPE,
-                       HostBatch, Metadata, pack_batch, unpack_row)
+from .metadata import (ACL_DTYPE, DELETE_SUPERSEDED, FETCH_LIVE, FILTER_DELETED, FILTER_TOMBSTONE, INFO_DTYPE,
+                       LIST_LATEST, LIST_REVERSE, META_DTYPE, HostBatch, Metadata, pack_batch, unpack_row)
 
 StorageVersion = 1  # object.go:14
 
@@ -448,6 +448,44 @@ class Codec:
         torch = _torch()
         return (values[:val_cap] if val_cap else None, val_off[:8 * (cap + 1)].view(torch.int64),
                 val_total[:8].view(torch.int64), status[:4 * cap].view(torch.int32))
+
+    def filter_workspace(self, cap: int):
+        """The workspace of filter_rows for a list of cap rows (honu_key_filter_workspace)."""
+        nbytes = int(self.lib.honu_key_filter_workspace(cap))
+        return self._empty(nbytes), nbytes
+
+    def filter_rows(self, rows, range_off, total, cap: int, tombstones: bool = False, deleted=None, keys=None):
+        """The live-object filter over the rows of list_keys, which stay on
+        the device with their offsets and total: an object deleted with a
+        tombstone version "will not be returned in list queries or retrieval"
+        (collection.go:132-134; Retrieve: "not found", collection.go:97-101).
+        With `tombstones` a row flagged LIST_ROW_TOMBSTONE goes (the list was
+        made with `info`); with `deleted` ((valid, n, obj_off, latest, objects,
+        info): the column's valid count and rows, key_objects' outputs and the
+        decode's record info) every row of an object whose latest version is a
+        tombstone goes, wherever that version lies; with neither the list is
+        copied. Returns (rows, range_off, total, keys) in the forms list_keys
+        returns them, on the device: the rows that stay, in order, of which
+        `total` are written, the rows kept before each range and their total,
+        HEAD on the first kept row of each range, and the kept rows' keys when
+        `keys` (list_keys' keys) is given, else None. The result passes
+        straight to fetch_objects; a range that comes out empty is Retrieve's
+        "not found"."""
+        m = range_off.numel() * range_off.element_size() // 8 - 1
+        flags = (FILTER_TOMBSTONE if tombstones else 0) | (FILTER_DELETED if deleted is not None else 0)
+        valid, n, obj_off, latest, objects, info = deleted if deleted is not None else (None, 0, None, None, None, None)
+        rows_out = self._empty(16 * cap)
+        range_off_out, total_out = self._empty(8 * (m + 1)), self._empty(8)
+        keys_out = self._empty(29 * cap) if keys is not None else None
+        work, work_bytes = self.filter_workspace(cap)
+        _lib.check(self.lib.honu_key_filter(
+            self.ctx, _lib.ptr(rows), _lib.ptr(keys), _lib.ptr(range_off), m, _lib.ptr(total), cap, flags,
+            _lib.ptr(valid), n, _lib.ptr(obj_off), _lib.ptr(latest), _lib.ptr(objects), _lib.ptr(info),
+            _lib.ptr(rows_out), _lib.ptr(keys_out), _lib.ptr(range_off_out), _lib.ptr(total_out), _lib.ptr(work),
+            work_bytes, self.stream), "honu_key_filter")
+        torch = _torch()
+        return (rows_out[:16 * cap].view(torch.int32).view(cap, 4), range_off_out[:8 * (m + 1)].view(torch.int64),
+                total_out[:8].view(torch.int64), keys_out[:29 * cap] if keys is not None else None)
 
 
 _default: Optional[Codec] = None

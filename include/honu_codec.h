@@ -23,6 +23,7 @@
  *   bucket.Delete (a batch)     store.go:378-383, 399-404 honu_key_delete (stable compaction of the sorted column)
  *   Cursor.Next / Prev (batch)  iterator/cursor.go:57-89  honu_key_list (the rows of a batch of seek ranges, packed)
  *   Cursor.Object() (batch)     iterator/cursor.go:31-38  honu_key_fetch (the records the listed rows name, a CSR arena)
+ *   deleted objects not listed  collection.go:132-134, 97-101  honu_key_filter (stable compaction of the listed rows)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -819,9 +820,10 @@ uint64_t honu_sizeof_list_row(void);
  * Tombstones. Collection.Delete's comment says an object with a tombstone
  * version "will not be returned in list queries" (collection.go:132-134).
  * Here a tombstone is FLAGGED (HONU_LIST_ROW_TOMBSTONE, when d_info is
- * given), not filtered: the filter, a compaction of the rows, is not built
- * (honu_key_fetch with HONU_FETCH_LIVE fetches nothing for a flagged row and
- * leaves the row in place).
+ * given), not filtered: honu_key_filter compacts the flagged rows, or every
+ * row of a deleted object, out of the list (honu_key_fetch with
+ * HONU_FETCH_LIVE fetches nothing for a flagged row and leaves the row in
+ * place).
  * Outputs. d_range_off[0, m] is the exclusive scan of the c_q and
  * d_range_off[m] = d_total[0] = total, a 64-bit sum (overlapping ranges can
  * exceed n). w = min(total, cap): only output rows g < w are written. Row g
@@ -883,7 +885,8 @@ enum {
  * HONU_LIST_ROW_TOMBSTONE in d_rows[g].flags its length is 0 and its status
  * HONU_OK, whatever r is, and d_rec_off is not read: Object() returning nil
  * for the object that a listing does not return (collection.go:132-134). The
- * row stays in place; compacting it away is not built. Otherwise r >= nrec
+ * row stays in place; honu_key_filter before the fetch takes it out of the
+ * list. Otherwise r >= nrec
  * (HONU_SEEK_NONE of a list made without d_order included) gives length 0 and
  * HONU_ERR_INPUT; otherwise a = d_rec_off[r], b = d_rec_off[r + 1] give length
  * b - a and HONU_OK when a <= b <= rec_bytes, else length 0 and
@@ -921,6 +924,107 @@ int32_t honu_key_fetch(honu_ctx *ctx, const honu_list_row *d_rows, const uint64_
                        uint64_t rec_bytes, uint32_t flags,
                        uint64_t *d_val_off, int32_t *d_status,
                        uint8_t *d_values, uint64_t val_cap, uint64_t *d_val_total, void *stream);
+
+/* honu_key_filter flags */
+enum {
+    HONU_FILTER_TOMBSTONE = 1u << 0, /* drop a row whose flags carry HONU_LIST_ROW_TOMBSTONE */
+    HONU_FILTER_DELETED   = 1u << 1  /* drop every row of an object whose LATEST version is a tombstone */
+};
+
+/* Bytes of honu_key_filter's workspace for a list of cap rows: a multiple of
+ * 256, monotonic in cap, 0 for cap == 0; needs no device. */
+uint64_t honu_key_filter_workspace(uint64_t cap);
+
+/* The live-object filter over listed rows. Collection.Delete's comment says
+ * that an object deleted with a tombstone version "will not be returned in
+ * list queries or retrieval" (collection.go:132-134), and Retrieve of it is
+ * "not found" (collection.go:97-101, 53-54). honu_key_list only flags such
+ * rows; this call takes them out: a stable compaction of the list's rows, with
+ * the ranges' offsets and the HEAD flags recomputed. Its output is a list
+ * again (d_rows_out, d_range_off_out, d_total_out and, optionally, the keys),
+ * so honu_key_fetch and the decoders take it unchanged: a range that comes out
+ * empty is Retrieve's "not found", and the decoded batch holds exactly the
+ * objects a reference listing returns. Every count stays on the device.
+ * Rows that take part. d_rows, d_range_off[0, m], d_total and cap are what
+ * honu_key_list wrote and was given; d_keys, when given, its d_keys_out. w =
+ * min(d_total[0], cap) is read on the device and only rows g < w take part: a
+ * truncated list is filtered as far as it was written.
+ * Which rows go. Row g goes when any flag that is set says so; with flags == 0
+ * the call copies the list.
+ * HONU_FILTER_TOMBSTONE: the row goes when d_rows[g].flags carries
+ * HONU_LIST_ROW_TOMBSTONE (the list was made with d_info). Nothing else is
+ * read. This is the row's own record: right for a list whose rows are latest
+ * versions (HONU_LIST_LATEST, or REVERSE with limit 1 over object ranges).
+ * HONU_FILTER_DELETED: the object-level answer, for Versions of a deleted
+ * object and for a List() over the whole column without LATEST, where a
+ * range need not end on the object's latest version. It reads the column's
+ * d_valid and n and what honu_key_objects wrote for it (d_obj_off, d_latest,
+ * d_objects), and the d_info the list's records index: v = min(d_valid[0], n)
+ * and objects = min(d_objects[0], n). A row with pos >= v names no object and
+ * stays, and so does every row when objects == 0. Otherwise j is the object
+ * with d_obj_off[j] <= pos < d_obj_off[j + 1], found by an upper bound of pos
+ * over d_obj_off[1..objects], every offset clamped to v, as the list's LATEST
+ * mode reads them (a pos at or past the last offset reads the last object). r
+ * = d_latest[j]; an r that is not below n reads info row n - 1, the convention
+ * of honu_key_seek and honu_key_list. The row goes when d_info[r].tombstone !=
+ * 0. So every version row of a deleted object goes, its live older versions
+ * included; a tombstone version of an object whose latest version is live
+ * stays (Versions() "includes tombstone versions", collection.go:106-107);
+ * and a row of an object whose latest row lies outside the row's range is
+ * still judged by the column's latest row.
+ * Outputs. The kept rows go to d_rows_out[0, kept) in input order. range, pos,
+ * record and the TOMBSTONE bit are unchanged; every other flag bit but HEAD is
+ * copied too. d_range_off_out[q], for q in [0, m), is the number of kept rows
+ * among the rows below min(d_range_off[q], w), so over a list's offsets it is
+ * the exclusive scan of the kept counts per range; d_range_off_out[m] =
+ * d_total_out[0] = kept, whatever d_range_off[m] holds. HONU_LIST_ROW_HEAD is
+ * recomputed: set on the kept row that lands on d_range_off_out[min(range, m -
+ * 1)] of its own range field and cleared on every other (with m == 0 on all),
+ * which over a list is exactly the first kept row of each range: HEAD moves
+ * to the next kept row when a range's first row goes, and a range that
+ * vanishes has none. When both key pointers are given, d_keys_out + 29 k
+ * receives the 29 key bytes of the k-th kept row (any byte alignment).
+ * The write set is exactly d_rows_out[0, kept), d_keys_out[0, 29 kept),
+ * d_range_off_out[0, m + 1), d_total_out[0] and the workspace. Inputs are
+ * unchanged; the outputs must not overlap the inputs. With cap == 0 only the
+ * m + 1 offsets and the total (all 0) are written.
+ * Every index derived from device data is clamped to cap, m, n or v: pos,
+ * range, an offset of d_range_off or d_obj_off, d_latest[j]. Garbage there
+ * may give wrong rows, never an access outside the arrays or a search that
+ * does not end.
+ * d_work is honu_key_filter_workspace(cap) bytes, 256-byte aligned (unused,
+ * and NULL allowed, when that is 0). The kept counts of the tiles, one per
+ * "filter_tile" rows, are summed by the context's scan (the one behind
+ * honu_exclusive_scan), whose state covers honu_ctx_max_records rows: cap may
+ * be up to "filter_tile" * honu_ctx_max_records (1024 rows per record the
+ * context was created for), and one context serves one stream at a time, as
+ * for honu_key_list and honu_key_delete. Asynchronous on `stream`, no host
+ * synchronisation, no allocation; the grid is sized from cap, never from a
+ * count on the device; replays from a captured graph, also after d_total, the
+ * rows or the info were changed on the device between replays.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for cap, m or n above 2^32
+ * - 1, or for cap above "filter_tile" * honu_ctx_max_records (more tiles than
+ * the context's scan covers); HONU_E_ARG for a NULL ctx, d_range_off, d_total,
+ * d_range_off_out or d_total_out, a NULL d_rows or d_rows_out with cap > 0,
+ * HONU_FILTER_DELETED without all of d_valid, d_obj_off, d_latest, d_objects
+ * and d_info, one of d_keys and d_keys_out without the other, unknown flag
+ * bits, d_rows_out == d_rows, d_range_off_out == d_range_off, d_total_out ==
+ * d_total or d_keys_out == d_keys, work_bytes below
+ * honu_key_filter_workspace(cap), a NULL or misaligned (256) workspace when
+ * that size is not 0, or a misaligned pointer (4 bytes: d_latest; 8 bytes:
+ * d_range_off, d_total, d_valid, d_obj_off, d_objects, d_info,
+ * d_range_off_out, d_total_out; 16 bytes: d_rows, d_rows_out).
+ * The get-only param "filter_tile" is the list rows one workgroup takes. */
+int32_t honu_key_filter(honu_ctx *ctx, const honu_list_row *d_rows,
+                        const uint8_t *d_keys /* optional, 29 B per row */,
+                        const uint64_t *d_range_off, uint64_t m, const uint64_t *d_total,
+                        uint64_t cap, uint32_t flags,
+                        /* HONU_FILTER_DELETED only: */
+                        const uint64_t *d_valid, uint64_t n, const uint64_t *d_obj_off,
+                        const uint32_t *d_latest, const uint64_t *d_objects,
+                        const honu_record_info *d_info,
+                        honu_list_row *d_rows_out, uint8_t *d_keys_out, uint64_t *d_range_off_out,
+                        uint64_t *d_total_out, void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
