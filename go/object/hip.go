@@ -19,6 +19,7 @@
 //	sort.Sort(keys.Keys)      keys/keys.go:126-130 -> (*Codec).SortKeys
 //	object version ranges     keys/keys.go:73-92   -> (*Codec).KeyObjects
 //	Cursor.Seek, Has, Exists  iterator/cursor.go:44-55, collection.go:47-65 -> (*Codec).SeekKeys, Has, Exists
+//	pid.Next, Tombstone       lamport/pid.go:10-15, metadata/collection.go:56-63 -> (*Codec).NextVersions
 package object
 
 /*
@@ -39,6 +40,7 @@ import (
 	"unsafe"
 
 	"go.rtnl.ai/honu/pkg/region"
+	"go.rtnl.ai/honu/pkg/store/keys"
 	"go.rtnl.ai/honu/pkg/store/lamport"
 	"go.rtnl.ai/honu/pkg/store/lani"
 	"go.rtnl.ai/honu/pkg/store/metadata"
@@ -1167,6 +1169,90 @@ func (c *Codec) FilterRows(o *KeyOrder, rows []ListRow, offsets []uint64, tombst
 		kept[g] = ListRow{uint32(r._range), uint32(r.pos), uint32(r.record), uint32(r.flags)}
 	}
 	return kept, keptOffsets, nil
+}
+
+// NextOp says which of Collection's writes a batch of NextVersions is.
+type NextOp uint32
+
+const (
+	NextCreate NextOp = C.HONU_NEXT_CREATE // Collection.Create, collection.go:75-95
+	NextUpdate NextOp = C.HONU_NEXT_UPDATE // Collection.Update, collection.go:112-121
+	NextMerge  NextOp = C.HONU_NEXT_MERGE  // Collection.Merge, collection.go:123-130
+	NextDelete NextOp = C.HONU_NEXT_DELETE // Collection.Delete, collection.go:132-137
+)
+
+// Next is one request's answer from NextVersions (honu_next and its key).
+type Next struct {
+	Version      lamport.Scalar // the assigned version (Assigned)
+	Parent       lamport.Scalar // Version.Parent (HasParent)
+	ParentRecord uint32         // o.Order of the stored row that is the parent, C.HONU_SEEK_NONE otherwise
+	Flags        uint32         // C.HONU_NEXT_*
+	Key          keys.Key       // keys.New(id, &Version) when assigned
+}
+
+func (n Next) Assigned() bool  { return n.Flags&C.HONU_NEXT_ASSIGNED != 0 }
+func (n Next) HasParent() bool { return n.Flags&C.HONU_NEXT_HAS_PARENT != 0 }
+
+// NextVersions decides the version each of a batch of writes writes, which is
+// what every write of the store starts with: Store.Drop seeks the stored
+// version and calls meta.Tombstone(lamport.ProcessID(), region)
+// (store.go:361-395), pid.Next of the stored scalar with that scalar as Parent
+// (metadata/collection.go:56-63, lamport/pid.go:10-15); Create starts a history
+// at Scalar{PID: 0, VID: 1} (collection.go:87-92). The bodies of
+// Collection.Update, Merge and Delete are stubs upstream: op carries out their
+// doc comments (collection.go:112-137) with that code, the requests answered
+// as the calls would be one after the other (a second Update of an object
+// follows the first, a second Delete meets a deleted object). info, the
+// decode's record info rows on the device, lets a stored tombstone say "not
+// found"; without it every stored object is live. The keys of the assigned
+// rows go on to SortKeys and MergeKeys.
+//
+// UNCOMPILED, like the rest of this file. honu_key_next is exercised on the
+// GPU from Python (tests/test_gpu_key_next.py), graph capture included.
+func (c *Codec) NextVersions(o *KeyOrder, ids []ulid.ULID, op NextOp, pid lamport.PID, region uint32, now time.Time, info devBuf) ([]Next, error) {
+	m := uint64(len(ids))
+	if m == 0 {
+		return nil, nil
+	}
+	nextSize := uint64(C.honu_sizeof_next())
+	hReq, hOut, hKeys := pinned(uintptr(C.HONU_KEY_LEN*m)), pinned(uintptr(nextSize*m)), pinned(uintptr(C.HONU_KEY_LEN*m))
+	defer hReq.free()
+	defer hOut.free()
+	defer hKeys.free()
+	req := hReq.bytes()
+	for i, id := range ids {
+		copy(req[C.HONU_KEY_LEN*i:], keys.New(id, nil)[:17]) // the ObjectPrefix; the call reads no more
+	}
+	workBytes := uint64(C.honu_key_next_workspace(C.uint64_t(m)))
+	dReq, dOut, dKeys, dSt, work := device(hReq.n), device(hOut.n), device(hKeys.n), device(uintptr(4*m)), device(uintptr(workBytes))
+	for _, b := range []devBuf{dReq, dOut, dKeys, dSt, work} {
+		defer b.free()
+	}
+	for _, s := range []C.int32_t{
+		C.honu_memcpy_h2d(dReq.p, hReq.p, C.uint64_t(hReq.n), c.stream),
+		C.honu_key_next(c.ctx, (*C.uint8_t)(o.sorted.p), (*C.uint64_t)(o.valid.p), C.uint64_t(o.n),
+			(*C.uint32_t)(o.order.p), (*C.honu_record_info)(info.p), (*C.uint8_t)(dReq.p), nil, C.uint64_t(m),
+			C.uint32_t(op), C.uint32_t(pid), C.uint32_t(region), C.int64_t(now.UnixNano()), (*C.honu_next)(dOut.p),
+			(*C.uint8_t)(dKeys.p), (*C.int32_t)(dSt.p), nil, work.p, C.uint64_t(workBytes), c.stream),
+		C.honu_memcpy_d2h(hOut.p, dOut.p, C.uint64_t(hOut.n), c.stream),
+		C.honu_memcpy_d2h(hKeys.p, dKeys.p, C.uint64_t(hKeys.n), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_key_next", s); err != nil {
+			return nil, err
+		}
+	}
+	out := make([]Next, m)
+	all := hKeys.bytes()
+	for i, r := range unsafe.Slice((*C.honu_next)(hOut.p), m) {
+		out[i] = Next{
+			Version:      lamport.Scalar{PID: uint32(r.pid), VID: uint64(r.vid)},
+			Parent:       lamport.Scalar{PID: uint32(r.parent_pid), VID: uint64(r.parent_vid)},
+			ParentRecord: uint32(r.parent_record), Flags: uint32(r.flags),
+			Key: append(keys.Key{}, all[C.HONU_KEY_LEN*i:C.HONU_KEY_LEN*(i+1)]...),
+		}
+	}
+	return out, nil
 }
 
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&

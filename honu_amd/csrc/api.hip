@@ -171,6 +171,7 @@ uint64_t honu_sizeof_index(void) { return sizeof(honu_index); }
 uint64_t honu_sizeof_record_info(void) { return sizeof(honu_record_info); }
 uint64_t honu_sizeof_seek(void) { return sizeof(honu_seek); }
 uint64_t honu_sizeof_list_row(void) { return sizeof(honu_list_row); }
+uint64_t honu_sizeof_next(void) { return sizeof(honu_next); }
 const char *honu_last_error(void) { return g_last_error; }
 
 const char *honu_status_string(int32_t st) {
@@ -952,6 +953,40 @@ int32_t honu_key_filter(honu_ctx *ctx, const honu_list_row *d_rows, const uint8_
     HIPCHK(launch_key_filter(d_rows, d_keys, d_range_off, m, d_total, cap, flags, d_valid, n, d_obj_off, d_latest,
                              d_objects, d_info, d_rows_out, d_keys_out, d_range_off_out, d_total_out, d_work,
                              ctx->scan, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the version each of a batch of writes writes (lamport/pid.go:10-15;
+// collection.go:75-137; store.go:361-395)
+// ---------------------------------------------------------------------------
+uint64_t honu_key_next_workspace(uint64_t m) { return next_workspace_bytes(m); }
+
+int32_t honu_key_next(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_valid, uint64_t n,
+                      const uint32_t *d_order, const honu_record_info *d_info, const uint8_t *d_requests,
+                      const int32_t *d_req_status, uint64_t m, uint32_t op, uint32_t pid, uint32_t region,
+                      int64_t now, honu_next *d_out, uint8_t *d_keys_out, int32_t *d_key_status, honu_meta *d_meta,
+                      void *d_work, uint64_t work_bytes, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    // the requests are sorted with the context's scan state, which covers max_records rows
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || m > ctx->max_n) return HONU_E_WORKSPACE;
+    if (op > (uint32_t)HONU_NEXT_DELETE) return arg_fail("unknown op");
+    if (!d_valid || (n && !d_sorted)) return arg_fail("null d_valid or column");
+    if (m && (!d_requests || !d_out || !d_keys_out || !d_key_status))
+        return arg_fail("null requests, d_out, d_keys_out or d_key_status");
+    if (d_info && !d_order) return arg_fail("d_info needs d_order");
+    if (d_requests && d_keys_out == d_requests) return arg_fail("an output is an input");
+    if (!aligned(d_order, 4) || !aligned(d_req_status, 4) || !aligned(d_key_status, 4) || !aligned(d_out, 8) ||
+        !aligned(d_valid, 8) || !aligned(d_info, 8) || !aligned(d_meta, 8))
+        return arg_fail("order and statuses 4-byte / d_out, valid count, record info and rows 8-byte aligned");
+    const uint64_t need = next_workspace_bytes(m);
+    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_next_workspace(m)");
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    if (m == 0) return HONU_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_next(d_sorted, d_valid, n, d_order, d_info, d_requests, d_req_status, m, op, pid, region, now,
+                           d_out, d_keys_out, d_key_status, d_meta, d_work, ctx->scan, ctx->max_n,
+                           (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -331,6 +331,18 @@ hipError_t launch_key_filter(const honu_list_row *rows, const uint8_t *keys, con
                              uint64_t *range_off_out, uint64_t *total_out, void *work, const ScanState &S,
                              hipStream_t s);
 
+// next.hip: the version each of a batch of writes writes (lamport/pid.go:10-15; collection.go:75-137;
+// store.go:361-395): requests are 17-byte object prefixes in 29-byte rows, ranked among themselves through
+// launch_sort_keys and looked up in the resident column as honu_key_seek's 17-byte probes. n, m <= 2^32 - 1; m
+// must not exceed scan_rows, the rows the context's scan state covers (its max_records). The workspace is the
+// caller's (next_workspace_bytes(m)); order, info, rstatus and meta may be null
+uint64_t next_workspace_bytes(uint64_t m);
+hipError_t launch_key_next(const uint8_t *sorted, const uint64_t *valid, uint64_t n, const uint32_t *order,
+                           const honu_record_info *info, const uint8_t *req, const int32_t *rstatus, uint64_t m,
+                           uint32_t op, uint32_t pid, uint32_t region, int64_t now, honu_next *out, uint8_t *keys_out,
+                           int32_t *key_status, honu_meta *meta, void *work, const ScanState &S, uint64_t scan_rows,
+                           hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

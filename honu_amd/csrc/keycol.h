@@ -1,6 +1,7 @@
 // keycol.h — what the kernels over the ordered key column share: the sort
 // (sort.hip), the seek (seek.hip), the merge (merge.hip), the delete
-// (delete.hip), the list (list.hip) and the filter (filter.hip).
+// (delete.hip), the list (list.hip), the filter (filter.hip) and the version
+// assignment (next.hip).
 //   the packed key  a 29-byte key as 32 bytes read as eight big-endian words,
 //                   byte 0 the validity (0 valid, 1 not), bytes 1-29 the key,
 //                   bytes 30-31 zero. An unsigned compare of the words from
@@ -171,6 +172,38 @@ template <typename Yes> HONU_DEV uint32_t thread_bound(uint32_t lo, uint32_t hi,
         else hi = mid;
     }
     return lo;
+}
+
+// Both bounds of a probe by one thread (seek.hip, next.hip): the lower bound's
+// loop notes what each key it loads says about the upper bound, so the upper
+// bound's own loop starts from what is left (nothing, for a probe that is not
+// stored). pos: the first position in [lo, hi] whose key is >= p; end: the
+// first in [ulo, uhi] whose key is > p. The caller knows both brackets to hold
+// their answer; a position equal to a bracket's upper end is never loaded.
+// load(i, k) gives the masked packed key at position i.
+template <typename Load>
+HONU_DEV void seek_bounds(Load load, const uint32_t p[SORT_KEY_WORDS], uint32_t lo, uint32_t hi, uint32_t ulo,
+                          uint32_t uhi, uint32_t &pos, uint32_t &end) {
+    uint32_t k[SORT_KEY_WORDS];
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        load(mid, k);
+        const int c = cmp_packed(k, p);
+        if (c < 0) lo = mid + 1;
+        else hi = mid;
+        // what the same key says about the upper bound
+        if (c > 0) uhi = uhi < mid ? uhi : mid;
+        else ulo = ulo > mid + 1 ? ulo : mid + 1;
+    }
+    pos = lo;
+    ulo = ulo > pos ? ulo : pos;
+    while (ulo < uhi) {
+        const uint32_t mid = ulo + ((uhi - ulo) >> 1);
+        load(mid, k);
+        if (cmp_packed(k, p) <= 0) ulo = mid + 1;
+        else uhi = mid;
+    }
+    end = ulo;
 }
 
 }  // namespace honu

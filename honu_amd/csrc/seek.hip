@@ -40,35 +40,6 @@ uint32_t seek_fence() { return SEEK_FENCE; }
 uint64_t seek_auto_probes() { return SEEK_AUTO_PROBES; }
 uint64_t seek_auto_keys() { return SEEK_AUTO_KEYS; }
 
-// pos: the first position in [lo, hi] whose key is >= p; end: the first in
-// [ulo, uhi] whose key is > p. The caller knows both brackets to hold their
-// answer; a position equal to a bracket's upper end is never loaded. load(i, k)
-// gives the masked packed key at position i.
-template <typename Load>
-HONU_DEV void seek_bounds(Load load, const uint32_t p[SORT_KEY_WORDS], uint32_t lo, uint32_t hi, uint32_t ulo,
-                          uint32_t uhi, uint32_t &pos, uint32_t &end) {
-    uint32_t k[SORT_KEY_WORDS];
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        load(mid, k);
-        const int c = cmp_packed(k, p);
-        if (c < 0) lo = mid + 1;
-        else hi = mid;
-        // what the same key says about the upper bound
-        if (c > 0) uhi = uhi < mid ? uhi : mid;
-        else ulo = ulo > mid + 1 ? ulo : mid + 1;
-    }
-    pos = lo;
-    ulo = ulo > pos ? ulo : pos;
-    while (ulo < uhi) {
-        const uint32_t mid = ulo + ((uhi - ulo) >> 1);
-        load(mid, k);
-        if (cmp_packed(k, p) <= 0) ulo = mid + 1;
-        else uhi = mid;
-    }
-    end = ulo;
-}
-
 // one result row as five plain 4-byte stores
 HONU_DEV void seek_store(honu_seek *out, uint32_t pos, uint32_t end, uint32_t first, uint32_t latest,
                          uint32_t flags) {

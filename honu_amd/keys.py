@@ -27,11 +27,16 @@ form is Codec.fetch_objects (honu_key_fetch). filter() is the host statement
 of what a listing leaves out, the object deleted with a tombstone version that
 "will not be returned in list queries or retrieval" (collection.go:132-134),
 over scan()'s list; the batch form is Codec.filter_rows (honu_key_filter).
+next() is the host statement of what every write decides first, the version
+it writes: pid.Next of the stored latest version (lamport/pid.go:10-15,
+metadata/collection.go:56-63) for a batch of Creates, Updates, Merges or
+Deletes (collection.go:75-137) over such a list; the batch form is
+Codec.next_versions (honu_key_next).
 """
 from __future__ import annotations
 
 import bisect
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, NamedTuple, Optional, Sequence
 
 from .metadata import Scalar
 
@@ -292,6 +297,98 @@ def filter(sorted_keys: Sequence[bytes], visits: Iterable, tomb, order: Optional
         if 0 <= p < n and (order is None or p < len(order)) and tomb(p if order is None else int(order[p])):
             continue
         out.append((q, pos))
+    return out
+
+
+class Next(NamedTuple):
+    """One request's answer from next(): the honu_next row and its key."""
+    scalar: Optional[Scalar]   # the assigned Version.Scalar, None unless NEXT_ASSIGNED
+    parent: Optional[Scalar]   # Version.Parent, None without NEXT_HAS_PARENT
+    parent_pos: Optional[int]  # the position of the parent in sorted_keys when it is the stored latest row
+    flags: int                 # metadata.NEXT_*
+    key: bytes                 # keys.New(ObjectID, scalar); the 17 request bytes and 12 zeros when not assigned
+
+
+def next(sorted_keys: Sequence[bytes], requests: Sequence[bytes], op: int, pid: int, live=None,
+         skip: Optional[Sequence] = None) -> List[Next]:
+    """The version each of a batch of writes writes, the first thing every
+    write of the reference decides: Store.Drop seeks the stored version and
+    calls meta.Tombstone(lamport.ProcessID(), region) (store.go:361-395), which
+    is pid.Next(&c.Version.Scalar) with the stored scalar as Parent
+    (metadata/collection.go:56-63, lamport/pid.go:10-15); Store.New and
+    Collection.Create start a history at Scalar{PID: 0, VID: 1}
+    (store.go:192-198, collection.go:87-92). The bodies of Collection.Update,
+    Merge, Delete and Retrieve are stubs upstream: what follows is their doc
+    comments (collection.go:112-137) carried out with the code of Drop, New,
+    Create and Tombstone, one `op` (metadata.NEXT_CREATE .. NEXT_DELETE) per
+    call, the requests applied in order as the Go calls would be one after the
+    other.
+
+    A request is a byte string of which only the first 17 bytes count, the
+    ObjectPrefix (keys.go:74-79). One that `skip` (a sequence of truth values)
+    skips gets NEXT_SKIPPED alone; any other whose byte 0 is not keyVersion
+    gets NEXT_BAD_KEY alone (Key.Check, keys.go:110-120); neither touches an
+    object. For every other request the object's rows are seek()'s [pos, end)
+    of the 17 bytes, FOUND = pos < end (Has, collection.go:47-51), the stored
+    latest scalar is version(sorted_keys[end - 1]), and LIVE = FOUND and
+    live(end - 1): `live` is a predicate on a position of sorted_keys that
+    says False for a tombstone (Exists as documented, collection.go:53-54),
+    None for no tombstones. FOUND and LIVE report the list as given. Then,
+    with the object's state as the requests before this one left it:
+      CREATE  an object that does not exist gets Scalar{0, 1} (collection.go:88,
+              not the process's PID) and no parent; else NEXT_EXISTS.
+      UPDATE  a live object gets pid_next(pid, latest), Parent = latest; else
+              NEXT_NOT_FOUND.
+      MERGE   an object that exists, deleted or not, as UPDATE; one that does
+              not gets pid_next(pid, None) and no parent.
+      DELETE  a live object gets pid_next(pid, latest), Parent = latest,
+              NEXT_TOMBSTONE, and is deleted from then on; else NEXT_NOT_FOUND.
+    So request r of an object (its rank among the counted requests with the
+    same 17 bytes) with stored latest (P, V) gets VID V + 1 + r and Parent
+    (P, V) for r == 0, (pid, V + r) after. VIDs are Go's uint64 and wrap as
+    they do; once an object's VID has passed 2^64 - 1 in this call its rows
+    carry NEXT_WRAPPED. parent_pos is end - 1 where the parent is that stored
+    row. The batch form on the GPU is Codec.next_versions (honu_key_next in
+    include/honu_codec.h), which equals this bit for bit."""
+    from .metadata import (NEXT_ASSIGNED, NEXT_BAD_KEY, NEXT_CREATE, NEXT_DELETE, NEXT_EXISTS, NEXT_FOUND,
+                           NEXT_HAS_PARENT, NEXT_LIVE, NEXT_MERGE, NEXT_NOT_FOUND, NEXT_SKIPPED, NEXT_TOMBSTONE,
+                           NEXT_UPDATE, NEXT_WRAPPED, pid_next)
+    if op not in (NEXT_CREATE, NEXT_UPDATE, NEXT_MERGE, NEXT_DELETE):
+        raise ValueError("unknown op")
+    state = {}  # prefix -> [exists, live, latest scalar, its position while it is the stored row, wrapped]
+    out: List[Next] = []
+    for i, req in enumerate(requests):
+        prefix = bytes(req)[:PREFIX_SIZE]
+        unassigned = prefix + bytes(KEY_SIZE - PREFIX_SIZE)
+        if skip is not None and skip[i]:
+            out.append(Next(None, None, None, NEXT_SKIPPED, unassigned))
+            continue
+        if len(prefix) != PREFIX_SIZE:
+            raise ErrBadSize()
+        if prefix[0] != KEY_VERSION:
+            out.append(Next(None, None, None, NEXT_BAD_KEY, unassigned))
+            continue
+        pos, end = seek(sorted_keys, prefix)
+        found = pos < end
+        alive = found and (live is None or bool(live(end - 1)))
+        flags = (NEXT_FOUND if found else 0) | (NEXT_LIVE if alive else 0)
+        st = state.setdefault(prefix, [found, alive, version(bytes(sorted_keys[end - 1])) if found else None,
+                                       end - 1 if found else None, False])
+        if op == NEXT_CREATE:
+            if st[0]:
+                out.append(Next(None, None, None, flags | NEXT_EXISTS, unassigned))
+                continue
+            scalar, parent, parent_pos = Scalar(PID=0, VID=1), None, None
+        elif op == NEXT_MERGE or st[1]:
+            scalar, parent, parent_pos = pid_next(pid, st[2]), st[2], st[3]
+            st[4] = st[4] or (parent is not None and scalar.VID < parent.VID)
+        else:
+            out.append(Next(None, None, None, flags | NEXT_NOT_FOUND, unassigned))
+            continue
+        st[0], st[1], st[2], st[3] = True, op != NEXT_DELETE, scalar, None
+        flags |= NEXT_ASSIGNED | (NEXT_HAS_PARENT if parent is not None else 0)
+        flags |= (NEXT_TOMBSTONE if op == NEXT_DELETE else 0) | (NEXT_WRAPPED if st[4] else 0)
+        out.append(Next(scalar, parent, parent_pos, flags, new(prefix[1:], scalar)))
     return out
 
 

@@ -75,6 +75,14 @@ LIST_ROW_HEAD, LIST_ROW_TOMBSTONE = 1 << 0, 1 << 1    # honu_list_row.flags
 FETCH_LIVE = 1 << 0  # honu_key_fetch flag (Codec.fetch_objects): rows flagged LIST_ROW_TOMBSTONE fetch nothing
 # honu_key_filter flags (Codec.filter_rows): drop rows flagged LIST_ROW_TOMBSTONE; drop every row of an object whose latest version is a tombstone
 FILTER_TOMBSTONE, FILTER_DELETED = 1 << 0, 1 << 1
+# honu_next: one row of honu_key_next per request (Codec.next_versions)
+NEXT_DTYPE = np.dtype(
+    {"names": ["vid", "parent_vid", "pid", "parent_pid", "parent_record", "flags"],
+     "formats": ["<u8", "<u8", "<u4", "<u4", "<u4", "<u4"], "offsets": [0, 8, 16, 20, 24, 28], "itemsize": 32}
+)
+NEXT_CREATE, NEXT_UPDATE, NEXT_MERGE, NEXT_DELETE = range(4)  # honu_key_next ops: Collection's writes
+(NEXT_ASSIGNED, NEXT_HAS_PARENT, NEXT_TOMBSTONE, NEXT_FOUND, NEXT_LIVE, NEXT_NOT_FOUND, NEXT_EXISTS, NEXT_BAD_KEY,
+ NEXT_SKIPPED, NEXT_WRAPPED) = (1 << b for b in range(10))  # honu_next.flags
 
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1
@@ -111,6 +119,13 @@ def _b2s(b: bytes) -> str:
 class Scalar:  # lamport/scalar.go:25-28
     PID: int = 0
     VID: int = 0
+
+
+def pid_next(pid: int, v: Optional[Scalar] = None) -> Scalar:
+    """PID.Next (lamport/pid.go:10-15; lamport.Next, pid.go:42-54, with the
+    process's PID): the scalar that follows v for this process, VID 1 after
+    nil. The VID is Go's uint64 and wraps as it does."""
+    return Scalar(PID=int(pid) & 0xFFFFFFFF, VID=1 if v is None else (int(v.VID) + 1) & 0xFFFFFFFFFFFFFFFF)
 
 
 @dataclass

@@ -487,6 +487,41 @@ class Codec:
         return (rows_out[:16 * cap].view(torch.int32).view(cap, 4), range_off_out[:8 * (m + 1)].view(torch.int64),
                 total_out[:8].view(torch.int64), keys_out[:29 * cap] if keys is not None else None)
 
+    def next_workspace(self, m: int):
+        """The workspace of next_versions for m requests (honu_key_next_workspace)."""
+        nbytes = int(self.lib.honu_key_next_workspace(m))
+        return self._empty(nbytes), nbytes
+
+    def next_versions(self, sorted_keys, valid, requests, op: int, pid: int, region: int = 0, now: int = 0,
+                      order=None, info=None, req_status=None, meta=None, m: Optional[int] = None):
+        """The version each of a batch of writes writes (pid.Next of the
+        stored latest version, lamport/pid.go:10-15, as Tombstone() uses it,
+        metadata/collection.go:56-63; Collection.Create, Update, Merge,
+        Delete, collection.go:75-137, whose bodies are stubs upstream and
+        whose doc comments `op` carries out: metadata.NEXT_CREATE ..
+        NEXT_DELETE), for m requests (the first 17 bytes of each 29-byte row
+        of `requests`) over sort_keys' sorted column and valid count, which
+        stay on the device; keys.next is the host statement. `order`
+        (sort_keys') gives parent_record, `info` (the decode's record info;
+        needs `order`) lets a stored tombstone say "not found"; requests whose
+        status is not OK are SKIPPED. `meta` (m honu_meta rows on the device)
+        is stamped in place with the assigned version, parent, tombstone,
+        `region`, the ObjectID and `now` as the timestamps. Returns (rows:
+        honu_next as a uint8 view of shape (m, 32), metadata.NEXT_DTYPE;
+        keys: 29 bytes per request; key_status: int32[m], OK on assigned
+        rows), on the device: keys and key_status are sort_keys' input as they
+        stand, and its output merge_keys'."""
+        n = sorted_keys.numel() // 29
+        if m is None:
+            m = requests.numel() // 29
+        out, keys, key_status = self._empty(32 * m), self._empty(29 * m), self._empty(4 * m)
+        work, work_bytes = self.next_workspace(m)
+        _lib.check(self.lib.honu_key_next(
+            self.ctx, _lib.ptr(sorted_keys), _lib.ptr(valid), n, _lib.ptr(order), _lib.ptr(info), _lib.ptr(requests),
+            _lib.ptr(req_status), m, op, pid, region, now, _lib.ptr(out), _lib.ptr(keys), _lib.ptr(key_status),
+            _lib.ptr(meta), _lib.ptr(work), work_bytes, self.stream), "honu_key_next")
+        return out[:32 * m].view(m, 32), keys[:29 * m], key_status[:4 * m].view(_torch().int32)
+
 
 _default: Optional[Codec] = None
 
