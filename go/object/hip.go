@@ -20,6 +20,7 @@
 //	object version ranges     keys/keys.go:73-92   -> (*Codec).KeyObjects
 //	Cursor.Seek, Has, Exists  iterator/cursor.go:44-55, collection.go:47-65 -> (*Codec).SeekKeys, Has, Exists
 //	pid.Next, Tombstone       lamport/pid.go:10-15, metadata/collection.go:56-63 -> (*Codec).NextVersions
+//	lamport.Compare, two replicas  lamport/scalar.go:15-78, keys/keys.go:35-36 -> (*Codec).CompareKeys
 package object
 
 /*
@@ -1253,6 +1254,87 @@ func (c *Codec) NextVersions(o *KeyOrder, ids []ulid.ULID, op NextOp, pid lampor
 		}
 	}
 	return out, nil
+}
+
+// Compared is one object's answer from CompareKeys: a honu_seek row and the
+// peer's row.
+type Compared struct {
+	Seek        // [Pos, End): my versions of the object later than anything the peer holds; Flags also C.HONU_CMP_*
+	Peer uint32 // the position of the peer's latest row of the object in its order (C.HONU_SEEK_NONE without PeerHas)
+}
+
+func (r Compared) PeerHas() bool  { return r.Flags&C.HONU_CMP_PEER_HAS != 0 }
+func (r Compared) Later() bool    { return r.Flags&C.HONU_CMP_LATER != 0 }
+func (r Compared) Earlier() bool  { return r.Flags&C.HONU_CMP_EARLIER != 0 }
+func (r Compared) Equal() bool    { return r.Flags&C.HONU_CMP_EQUAL != 0 }
+func (r Compared) Forked() bool   { return r.PeerHas() && r.Flags&C.HONU_CMP_ANCESTOR == 0 }
+
+// CompareCounts is honu_key_compare's d_counts.
+type CompareCounts struct{ Objects, OnlyMine, Later, Earlier, Equal, Forks uint64 }
+
+// CompareKeys decides, for every object of the local order, which side holds
+// its later version when two replicas meet: a lamport.Scalar "uses a 'latest
+// writer wins' policy to determine how to solve conflicts"
+// (lamport/scalar.go:15-24), lamport.Compare is the happens-before test
+// (scalar.go:47-78), and bytes.Compare of two keys of one object is
+// lamport.Compare of their versions (keys/keys.go:35-36). peer is the order of
+// the peer's keys, whole or a digest of one key per object, its latest. One row
+// per object of mine, in key order: [Pos, End) are the versions
+// latest-writer-wins sends, and the seeks pass to ListKeys and FetchObjects as
+// they are. PeerHas without the ancestor bit is a forked write, the branch
+// that "can be detected later" (collection.go:77-79); for an Earlier object
+// that needs the peer's whole order. The objects only the peer has are the
+// rows without PeerHas of CompareKeys(peer, mine). mine is an order that
+// SortKeys made (its objects are cut from its key column, as in KeyObjects).
+//
+// UNCOMPILED, like the rest of this file. honu_key_compare is exercised on the
+// GPU from Python (tests/test_gpu_key_compare.py), graph capture included.
+func (c *Codec) CompareKeys(mine, peer *KeyOrder) ([]Compared, CompareCounts, error) {
+	var counts CompareCounts
+	na := mine.n
+	workBytes := uint64(C.honu_key_compare_workspace(C.uint64_t(na)))
+	dOff, dObjects := device(uintptr(8*(na+1))), device(8)
+	dOut, dPeer, dCounts, dWork := device(uintptr(uint64(C.honu_sizeof_seek())*na)), device(uintptr(4*na)), device(64), device(uintptr(workBytes))
+	hOut, hPeer, hCounts := pinned(dOut.n), pinned(dPeer.n), pinned(64)
+	for _, d := range []devBuf{dOff, dObjects, dOut, dPeer, dCounts, dWork} {
+		defer d.free()
+	}
+	for _, h := range []hostBuf{hOut, hPeer, hCounts} {
+		defer h.free()
+	}
+	for _, s := range []C.int32_t{
+		C.honu_key_objects(c.ctx, (*C.uint8_t)(mine.keys.p), (*C.uint32_t)(mine.order.p), (*C.uint64_t)(mine.valid.p),
+			C.uint64_t(na), (*C.uint64_t)(dOff.p), nil, (*C.uint64_t)(dObjects.p), mine.work.p,
+			C.uint64_t(mine.workBytes), c.stream),
+		C.honu_key_compare(c.ctx, (*C.uint8_t)(mine.sorted.p), (*C.uint32_t)(mine.order.p), (*C.uint64_t)(mine.valid.p),
+			C.uint64_t(na), (*C.uint64_t)(dOff.p), (*C.uint64_t)(dObjects.p), (*C.uint8_t)(peer.sorted.p),
+			(*C.uint64_t)(peer.valid.p), C.uint64_t(peer.n), (*C.honu_seek)(dOut.p), (*C.uint32_t)(dPeer.p),
+			(*C.uint64_t)(dCounts.p), dWork.p, C.uint64_t(workBytes), c.stream),
+		C.honu_memcpy_d2h(hCounts.p, dCounts.p, 64, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("honu_key_compare", s); err != nil {
+			return nil, counts, err
+		}
+	}
+	n := unsafe.Slice((*uint64)(hCounts.p), 8)
+	counts = CompareCounts{n[0], n[1], n[2], n[3], n[4], n[5]}
+	objects := counts.Objects
+	for _, s := range []C.int32_t{ // only what was written: `objects` rows
+		C.honu_memcpy_d2h(hOut.p, dOut.p, C.uint64_t(uint64(C.honu_sizeof_seek())*objects), c.stream),
+		C.honu_memcpy_d2h(hPeer.p, dPeer.p, C.uint64_t(4*objects), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err := call("download", s); err != nil {
+			return nil, counts, err
+		}
+	}
+	rows, at := unsafe.Slice((*C.honu_seek)(hOut.p), objects), unsafe.Slice((*uint32)(hPeer.p), objects)
+	out := make([]Compared, objects)
+	for j, r := range rows {
+		out[j] = Compared{Seek{uint32(r.pos), uint32(r.end), uint32(r.first), uint32(r.latest), uint32(r.flags)}, at[j]}
+	}
+	return out, counts, nil
 }
 
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&

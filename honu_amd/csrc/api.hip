@@ -371,6 +371,8 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "list_tile")) *value = list_tile();    // read only: output rows per workgroup of the list
     else if (!strcmp(name, "list_stage")) *value = list_stage();  // read only: range offsets a workgroup of the list stages in LDS
     else if (!strcmp(name, "filter_tile")) *value = filter_tile();  // read only: list rows per workgroup of the filter
+    else if (!strcmp(name, "compare_tile")) *value = compare_tile();    // read only: objects per workgroup of the compare
+    else if (!strcmp(name, "compare_stage")) *value = compare_stage();  // read only: peer rows a workgroup of the compare stages in LDS
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -987,6 +989,36 @@ int32_t honu_key_next(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_
     HIPCHK(launch_key_next(d_sorted, d_valid, n, d_order, d_info, d_requests, d_req_status, m, op, pid, region, now,
                            d_out, d_keys_out, d_key_status, d_meta, d_work, ctx->scan, ctx->max_n,
                            (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the versions of two columns compared object by object (lamport/scalar.go:15-78;
+// keys/keys.go:35-36)
+// ---------------------------------------------------------------------------
+uint64_t honu_key_compare_workspace(uint64_t na) { return compare_workspace_bytes(na); }
+
+int32_t honu_key_compare(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t *d_order_a,
+                         const uint64_t *d_valid_a, uint64_t na, const uint64_t *d_obj_off_a,
+                         const uint64_t *d_objects_a, const uint8_t *d_sorted_b, const uint64_t *d_valid_b,
+                         uint64_t nb, honu_seek *d_out, uint32_t *d_peer, uint64_t *d_counts, void *d_work,
+                         uint64_t work_bytes, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (na > 0xFFFFFFFFull || nb > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    if (!d_valid_a || !d_valid_b || !d_obj_off_a || !d_objects_a)
+        return arg_fail("null valid count, d_obj_off_a or d_objects_a");
+    if ((na && (!d_sorted_a || !d_out)) || (nb && !d_sorted_b)) return arg_fail("null column or d_out");
+    if (!aligned(d_out, 4) || !aligned(d_peer, 4) || !aligned(d_order_a, 4) || !aligned(d_counts, 8) ||
+        !aligned(d_valid_a, 8) || !aligned(d_valid_b, 8) || !aligned(d_obj_off_a, 8) || !aligned(d_objects_a, 8))
+        return arg_fail("rows, peer and order 4-byte / counts and offsets 8-byte aligned");
+    const uint64_t need = compare_workspace_bytes(na);
+    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_compare_workspace(na)");
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    // (make ab: HONU_COMPARE_STAGE below compare_stage sends more tiles down the unstaged path, 0 all of them)
+    const uint32_t stage = (uint32_t)env_int("HONU_COMPARE_STAGE", (int)compare_stage());
+    HIPCHK(launch_key_compare(d_sorted_a, d_order_a, d_valid_a, na, d_obj_off_a, d_objects_a, d_sorted_b, d_valid_b,
+                              nb, stage, d_out, d_peer, d_counts, d_work, (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -343,6 +343,19 @@ hipError_t launch_key_next(const uint8_t *sorted, const uint64_t *valid, uint64_
                            int32_t *key_status, honu_meta *meta, void *work, const ScanState &S, uint64_t scan_rows,
                            hipStream_t s);
 
+// compare.hip: the versions of two sorted columns compared object by object (lamport/scalar.go:15-78;
+// keys/keys.go:35-36): per object of A (obj_off, objects: launch_key_objects') one honu_seek row, the rows the
+// peer B is behind by and the HONU_CMP_* class. na, nb <= 2^32 - 1. The workspace is the caller's
+// (compare_workspace_bytes(na)); no scan state. stage: the rows of B a workgroup stages at most (compare_stage()
+// and no more); order_a, peer and counts may be null
+uint32_t compare_tile();
+uint32_t compare_stage();
+uint64_t compare_workspace_bytes(uint64_t na);
+hipError_t launch_key_compare(const uint8_t *sa, const uint32_t *order_a, const uint64_t *valid_a, uint64_t na,
+                              const uint64_t *obj_off, const uint64_t *objects, const uint8_t *sb,
+                              const uint64_t *valid_b, uint64_t nb, uint32_t stage, honu_seek *out, uint32_t *peer,
+                              uint64_t *counts, void *work, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -1,7 +1,7 @@
 // keycol.h — what the kernels over the ordered key column share: the sort
 // (sort.hip), the seek (seek.hip), the merge (merge.hip), the delete
-// (delete.hip), the list (list.hip), the filter (filter.hip) and the version
-// assignment (next.hip).
+// (delete.hip), the list (list.hip), the filter (filter.hip), the version
+// assignment (next.hip) and the comparison of two columns (compare.hip).
 //   the packed key  a 29-byte key as 32 bytes read as eight big-endian words,
 //                   byte 0 the validity (0 valid, 1 not), bytes 1-29 the key,
 //                   bytes 30-31 zero. An unsigned compare of the words from
@@ -204,6 +204,17 @@ HONU_DEV void seek_bounds(Load load, const uint32_t p[SORT_KEY_WORDS], uint32_t 
         else uhi = mid;
     }
     end = ulo;
+}
+
+// one honu_seek row (seek.hip, compare.hip) as five plain 4-byte stores
+HONU_DEV void seek_store(honu_seek *out, uint32_t pos, uint32_t end, uint32_t first, uint32_t latest,
+                         uint32_t flags) {
+    uint32_t *q = reinterpret_cast<uint32_t *>(out);
+    q[0] = pos;
+    q[1] = end;
+    q[2] = first;
+    q[3] = latest;
+    q[4] = flags;
 }
 
 }  // namespace honu

@@ -40,17 +40,6 @@ uint32_t seek_fence() { return SEEK_FENCE; }
 uint64_t seek_auto_probes() { return SEEK_AUTO_PROBES; }
 uint64_t seek_auto_keys() { return SEEK_AUTO_KEYS; }
 
-// one result row as five plain 4-byte stores
-HONU_DEV void seek_store(honu_seek *out, uint32_t pos, uint32_t end, uint32_t first, uint32_t latest,
-                         uint32_t flags) {
-    uint32_t *q = reinterpret_cast<uint32_t *>(out);
-    q[0] = pos;
-    q[1] = end;
-    q[2] = first;
-    q[3] = latest;
-    q[4] = flags;
-}
-
 HONU_DEV void seek_finish(honu_seek *out, uint32_t pos, uint32_t end, uint32_t valid, uint64_t n,
                           uint32_t probe_len, const uint32_t *__restrict__ order,
                           const honu_record_info *__restrict__ info) {

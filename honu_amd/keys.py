@@ -31,7 +31,10 @@ next() is the host statement of what every write decides first, the version
 it writes: pid.Next of the stored latest version (lamport/pid.go:10-15,
 metadata/collection.go:56-63) for a batch of Creates, Updates, Merges or
 Deletes (collection.go:75-137) over such a list; the batch form is
-Codec.next_versions (honu_key_next).
+Codec.next_versions (honu_key_next). compare() is the host statement of what
+two replicas decide when they meet, which side holds the later version of an
+object under "latest writer wins" (lamport/scalar.go:15-24, 47-78), over two
+such lists; the batch form is Codec.compare_keys (honu_key_compare).
 """
 from __future__ import annotations
 
@@ -389,6 +392,77 @@ def next(sorted_keys: Sequence[bytes], requests: Sequence[bytes], op: int, pid: 
         flags |= NEXT_ASSIGNED | (NEXT_HAS_PARENT if parent is not None else 0)
         flags |= (NEXT_TOMBSTONE if op == NEXT_DELETE else 0) | (NEXT_WRAPPED if st[4] else 0)
         out.append(Next(scalar, parent, parent_pos, flags, new(prefix[1:], scalar)))
+    return out
+
+
+class Compare(NamedTuple):
+    """One object's answer from compare(): the honu_seek row and the peer's row."""
+    pos: int             # [pos, end) of a: the object's versions later than anything the peer holds
+    end: int             # one past the object's latest row in a
+    flags: int           # metadata.SEEK_FOUND (pos < end) | metadata.CMP_*
+    peer: Optional[int]  # the position of the peer's latest row of the object in b, None without CMP_PEER_HAS
+
+
+def compare(a: Sequence[bytes], b: Sequence[bytes]) -> List[Compare]:
+    """The versions of two sorted lists of keys compared object by object:
+    what two replicas decide when they meet. A lamport.Scalar "uses a 'latest
+    writer wins' policy to determine how to solve conflicts"
+    (lamport/scalar.go:15-24), lamport.Compare is the happens-before test
+    (scalar.go:47-78), and a key stores its version big endian "to maintain
+    lexicographic sorting" (keys.go:35-36), so the order of two keys of one
+    object, Python's order of bytes, is lamport.Compare of their versions
+    (metadata.scalar_compare). `a` is the local list, `b` the peer's: its
+    whole list, or a digest of one key per object, its latest.
+
+    One answer per object of `a`, the groups of keys with the same first 17
+    bytes (ObjectPrefix, keys.go:74-79) in the list's order. For an object
+    with rows [a0, a1) and latest key K = a[a1 - 1], the peer's rows [b0, b1)
+    are seek(b, K[:17]), found by prefix equality and not by ObjectLimit's
+    wrapping limit[16]++ (keys.go:88-91), and only b[b1 - 1], the peer's
+    latest, decides:
+      end    a1.
+      pos    the first row of [a0, a1) whose key is greater than b[b1 - 1]
+             when the peer has the object, else a0: [pos, end) is what
+             latest-writer-wins sends, empty for an object equal or behind.
+      flags  SEEK_FOUND when pos < end; CMP_PEER_HAS when b0 < b1; one of
+             CMP_LATER (K > b[b1 - 1], or the peer has none), CMP_EARLIER and
+             CMP_EQUAL; CMP_ANCESTOR, with PEER_HAS only, when the older
+             side's latest key is a row of the newer side's range: a[pos - 1]
+             == b[b1 - 1] with pos > a0 for LATER, K in b[b0:b1] for EARLIER,
+             always for EQUAL. PEER_HAS without ANCESTOR is a forked write,
+             the branch that "can be detected later" (collection.go:77-79);
+             for EARLIER that is meaningful only when `b` is a whole list.
+    Equal keys form runs, as after merge(); the bounds above say which row of
+    a run counts. The objects only the peer has are the rows without
+    CMP_PEER_HAS of compare(b, a). The batch form on the GPU is
+    Codec.compare_keys (honu_key_compare in include/honu_codec.h), which
+    equals this."""
+    from .metadata import CMP_ANCESTOR, CMP_EARLIER, CMP_EQUAL, CMP_LATER, CMP_PEER_HAS, SEEK_FOUND
+    a = [bytes(k) for k in a]
+    b = [bytes(k) for k in b]
+    out: List[Compare] = []
+    a0 = 0
+    while a0 < len(a):
+        _, a1 = seek(a, a[a0][:PREFIX_SIZE])
+        mine = a[a1 - 1]
+        b0, b1 = seek(b, mine[:PREFIX_SIZE])
+        pos, flags, peer = a0, 0, None
+        if b0 < b1:
+            peer = b1 - 1
+            theirs = b[peer]
+            pos = bisect.bisect_right(a, theirs, a0, a1)
+            if mine > theirs:
+                flags = CMP_LATER | (CMP_ANCESTOR if pos > a0 and a[pos - 1] == theirs else 0)
+            elif mine < theirs:
+                at = bisect.bisect_left(b, mine, b0, b1)
+                flags = CMP_EARLIER | (CMP_ANCESTOR if at < b1 and b[at] == mine else 0)
+            else:
+                flags = CMP_EQUAL | CMP_ANCESTOR
+            flags |= CMP_PEER_HAS
+        else:
+            flags = CMP_LATER
+        out.append(Compare(pos, a1, flags | (SEEK_FOUND if pos < a1 else 0), peer))
+        a0 = a1
     return out
 
 

@@ -83,6 +83,11 @@ NEXT_DTYPE = np.dtype(
 NEXT_CREATE, NEXT_UPDATE, NEXT_MERGE, NEXT_DELETE = range(4)  # honu_key_next ops: Collection's writes
 (NEXT_ASSIGNED, NEXT_HAS_PARENT, NEXT_TOMBSTONE, NEXT_FOUND, NEXT_LIVE, NEXT_NOT_FOUND, NEXT_EXISTS, NEXT_BAD_KEY,
  NEXT_SKIPPED, NEXT_WRAPPED) = (1 << b for b in range(10))  # honu_next.flags
+# honu_key_compare (Codec.compare_keys) writes SEEK_DTYPE rows: SEEK_FOUND and these bits, above the seek's
+CMP_PEER_HAS, CMP_LATER, CMP_EARLIER, CMP_EQUAL, CMP_ANCESTOR = (1 << b for b in range(8, 13))
+# its d_counts: eight values, the last two zero
+CMP_COUNTS_DTYPE = np.dtype([(name, "<u8") for name in
+                             ("objects", "only_mine", "later", "earlier", "equal", "forks", "zero6", "zero7")])
 
 HAS_META = 1 << 0
 HAS_VERSION = 1 << 1
@@ -126,6 +131,16 @@ def pid_next(pid: int, v: Optional[Scalar] = None) -> Scalar:
     process's PID): the scalar that follows v for this process, VID 1 after
     nil. The VID is Go's uint64 and wraps as it does."""
     return Scalar(PID=int(pid) & 0xFFFFFFFF, VID=1 if v is None else (int(v.VID) + 1) & 0xFFFFFFFFFFFFFFFF)
+
+
+def scalar_compare(a: Optional[Scalar], b: Optional[Scalar]) -> int:
+    """lamport.Compare (lamport/scalar.go:47-78): -1, 0 or 1 as a happens
+    before, is, or happens after b: by VID, then by PID. nil is the zero
+    scalar. The order of two keys of one object (keys.py) is this order of
+    their versions."""
+    ka = (0, 0) if a is None else (int(a.VID), int(a.PID))
+    kb = (0, 0) if b is None else (int(b.VID), int(b.PID))
+    return (ka > kb) - (ka < kb)
 
 
 @dataclass

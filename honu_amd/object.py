@@ -522,6 +522,45 @@ class Codec:
             _lib.ptr(meta), _lib.ptr(work), work_bytes, self.stream), "honu_key_next")
         return out[:32 * m].view(m, 32), keys[:29 * m], key_status[:4 * m].view(_torch().int32)
 
+    def compare_workspace(self, na: int):
+        """The workspace of compare_keys for a local column of na rows (honu_key_compare_workspace)."""
+        nbytes = int(self.lib.honu_key_compare_workspace(na))
+        return self._empty(nbytes), nbytes
+
+    def compare_keys(self, sorted_a, order_a, valid_a, obj_off_a, objects_a, sorted_b, valid_b,
+                     want_peer: bool = False, want_counts: bool = True):
+        """The versions of two sorted columns compared object by object: what
+        two replicas decide when they meet under "latest writer wins"
+        (lamport/scalar.go:15-24; lamport.Compare, scalar.go:47-78, which is
+        bytes.Compare of two keys of one object, keys/keys.go:35-36). A is the
+        local column (sort_keys' / merge_keys' sorted column, order or None,
+        valid count) with key_objects' (obj_off, objects) over it, B the
+        peer's sorted column and valid count, whole or a digest of one key per
+        object; all stay on the device. keys.compare is the host statement.
+        Returns (rows: honu_seek as an int32 view of shape (na, 5), of which
+        `objects` are written: [pos, end) the versions of the object the peer
+        is behind by, first / latest their record indices, flags SEEK_FOUND and
+        metadata.CMP_*; peer: int32[na], the peer's latest row of each object
+        or SEEK_NONE, with `want_peer`, else None; counts: int64[8],
+        metadata.CMP_COUNTS_DTYPE, with `want_counts`, else None). The rows are
+        list_keys' `ranges` as they stand: compare -> list -> fetch gathers
+        what to send. The call writes `objects` rows and the host does not
+        know that count, so the rows are cleared first: the rows from
+        `objects` on are empty ranges to list_keys. The objects only the peer
+        has are the only-mine rows of the call with the sides exchanged."""
+        na, nb = sorted_a.numel() // 29, sorted_b.numel() // 29
+        out = self._empty(20 * na).zero_()
+        peer = self._empty(4 * na) if want_peer else None
+        counts = self._empty(64) if want_counts else None
+        work, work_bytes = self.compare_workspace(na)
+        _lib.check(self.lib.honu_key_compare(
+            self.ctx, _lib.ptr(sorted_a), _lib.ptr(order_a), _lib.ptr(valid_a), na, _lib.ptr(obj_off_a),
+            _lib.ptr(objects_a), _lib.ptr(sorted_b), _lib.ptr(valid_b), nb, _lib.ptr(out), _lib.ptr(peer),
+            _lib.ptr(counts), _lib.ptr(work), work_bytes, self.stream), "honu_key_compare")
+        torch = _torch()
+        return (out[:20 * na].view(torch.int32).view(na, 5), peer[:4 * na].view(torch.int32) if want_peer else None,
+                counts[:64].view(torch.int64) if want_counts else None)
+
 
 _default: Optional[Codec] = None
 

@@ -25,6 +25,7 @@
  *   Cursor.Object() (batch)     iterator/cursor.go:31-38  honu_key_fetch (the records the listed rows name, a CSR arena)
  *   deleted objects not listed  collection.go:132-134, 97-101  honu_key_filter (stable compaction of the listed rows)
  *   pid.Next, Tombstone (batch) lamport/pid.go:10-15, collection.go:75-137  honu_key_next (the version each write writes)
+ *   lamport.Compare (two columns) lamport/scalar.go:15-78, keys/keys.go:35-36  honu_key_compare (who is later, what to send, forks)
  *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -1158,6 +1159,101 @@ int32_t honu_key_next(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_
                       uint32_t op, uint32_t pid, uint32_t region, int64_t now,
                       honu_next *d_out, uint8_t *d_keys_out, int32_t *d_key_status,
                       honu_meta *d_meta /* optional */, void *d_work, uint64_t work_bytes, void *stream);
+
+/* honu_seek.flags of a row honu_key_compare wrote, beside HONU_SEEK_FOUND: above
+ * bit 7, so the seek bits keep their meaning. Exactly one of LATER, EARLIER and
+ * EQUAL is set. */
+enum {
+    HONU_CMP_PEER_HAS = 1u << 8,  /* the peer's column holds a row of the object: b0 < b1 */
+    HONU_CMP_LATER    = 1u << 9,  /* lamport.Compare(my latest, the peer's latest) > 0, or the peer has none */
+    HONU_CMP_EARLIER  = 1u << 10, /* lamport.Compare(my latest, the peer's latest) < 0 */
+    HONU_CMP_EQUAL    = 1u << 11, /* both hold the same latest version */
+    HONU_CMP_ANCESTOR = 1u << 12  /* PEER_HAS and the older side's latest key is a row of the newer side:
+                                     no fork. PEER_HAS without it is the branch of collection.go:77-79 */
+};
+
+/* Bytes of honu_key_compare's workspace for na rows of A: the tiles' class
+ * counts. A multiple of 256, monotonic in na, 0 for na == 0; needs no device. */
+uint64_t honu_key_compare_workspace(uint64_t na);
+
+/* The versions of two sorted key columns compared object by object: what two
+ * replicas decide when they meet. A lamport.Scalar "uses a 'latest writer
+ * wins' policy to determine how to solve conflicts" (lamport/scalar.go:15-24),
+ * lamport.Compare is the happens-before test (scalar.go:47-78), and a key
+ * stores the version big endian "to maintain lexicographic sorting"
+ * (keys/keys.go:35-36), so bytes.Compare of two keys of one object is
+ * lamport.Compare of their versions. Iterator.Object() "is also used for
+ * replication" (iterator/iterator.go:19-23); Collection.Create promises that
+ * "branches can be detected later" (collection.go:77-79). honu_amd/keys.py
+ * compare() is the host statement; this call equals it.
+ * Inputs. A is the local column, B the peer's: each what honu_sort_keys,
+ * honu_key_merge or honu_key_delete writes, 29-byte rows at any byte
+ * alignment, the valid rows [0, v), v = min(d_valid[0], n), read on the
+ * device. B may be the peer's whole column or a digest of it, one key per
+ * object, the peer's latest: only the last row of an object's range in B
+ * decides the class. A's objects are what honu_key_objects wrote for it
+ * (d_obj_off_a, na + 1 values readable; d_objects_a): objects =
+ * min(d_objects_a[0], na), and every offset is clamped to va.
+ * For object j of A let [a0, a1) be its rows, K = A[a1 - 1] its latest key and
+ * [b0, b1) the rows of B whose first 17 bytes are K's: prefix equality, not
+ * ObjectLimit's wrapping limit[16]++ (keys.go:88-91), as in honu_key_objects
+ * and honu_key_seek. d_out[j] is one honu_seek row, so honu_key_list takes
+ * d_out as its d_ranges (it reads pos, end and SKIPPED only; with m = na,
+ * which is all the host knows, the caller clears d_out before the call, so
+ * that the rows from `objects` on are empty ranges):
+ *   end     a1.
+ *   pos     with b0 < b1 the first row of [a0, a1) whose key is greater than
+ *           B[b1 - 1] over all 29 bytes (the upper bound), else a0. [pos, end)
+ *           are my versions later than anything the peer holds, what
+ *           latest-writer-wins sends; empty for an object that is equal or
+ *           behind.
+ *   first, latest  d_order_a[pos], d_order_a[end - 1] when d_order_a is given
+ *           and pos < end, else HONU_SEEK_NONE.
+ *   flags   HONU_SEEK_FOUND when pos < end; HONU_CMP_PEER_HAS when b0 < b1;
+ *           one of HONU_CMP_LATER (K above B[b1 - 1], or the peer has none),
+ *           HONU_CMP_EARLIER and HONU_CMP_EQUAL; HONU_CMP_ANCESTOR, with
+ *           PEER_HAS only: for LATER pos > a0 and A[pos - 1] == B[b1 - 1], for
+ *           EARLIER K is a row of B[b0, b1), for EQUAL always. PEER_HAS
+ *           without ANCESTOR is a forked write. For EARLIER that is meaningful
+ *           only when B is the peer's whole column: a digest holds no older
+ *           row to find K among, so every EARLIER object of a digest reads as
+ *           a fork. HONU_SEEK_SKIPPED is never set, nor any other seek bit.
+ * Equal keys form runs, as after a merge; the bounds above say which row of a
+ * run counts. An object whose rows are empty after the clamps (garbage
+ * offsets alone) gets pos = end = a1 and, when a1 is 0, no flag at all.
+ * d_peer (optional, room for na): d_peer[j] = b1 - 1, the peer's latest row,
+ * or HONU_SEEK_NONE without PEER_HAS. d_counts (optional, 8 values): objects
+ * compared; only mine (no PEER_HAS); LATER with PEER_HAS; EARLIER; EQUAL;
+ * forks (PEER_HAS without ANCESTOR); 0; 0. The sums are made without atomics
+ * and are the same every time. The objects only the peer has are the "only
+ * mine" rows of the call with the sides exchanged; there is no second mode.
+ * The exact per-key difference A \ B is honu_key_delete(A, B, 29).
+ * The write set is exactly d_out[0, objects), d_peer[0, objects), d_counts[0,
+ * 8) and the workspace. With na == 0 only d_counts (zeros) is written. Inputs
+ * are unchanged. Garbage in d_obj_off_a, d_objects_a or the valid counts may
+ * give wrong rows, never an access outside the na / nb rows or a search that
+ * does not end; pos <= end <= va always holds.
+ * d_work is honu_key_compare_workspace(na) bytes, 256-byte aligned (NULL
+ * allowed when that is 0). No use of the context's scan state: calls on
+ * different streams may share a context, as with honu_key_seek and
+ * honu_key_merge. Asynchronous on `stream`, no host synchronisation, no
+ * allocation; the grid is sized from na; replays from a captured graph, also
+ * after the counts were changed on the device between replays.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for na or nb above 2^32 -
+ * 1; HONU_E_ARG for a NULL ctx, d_valid_a, d_valid_b, d_obj_off_a or
+ * d_objects_a, a NULL d_sorted_a with na > 0 or d_sorted_b with nb > 0, a NULL
+ * d_out with na > 0, work_bytes below honu_key_compare_workspace(na), a NULL
+ * or misaligned (256) workspace when that size is not 0, or a misaligned
+ * pointer (4 bytes: d_out, d_peer, d_order_a; 8 bytes: d_counts, d_valid_a,
+ * d_valid_b, d_obj_off_a, d_objects_a).
+ * The get-only params "compare_tile" and "compare_stage" are the objects one
+ * workgroup takes and the rows of B it stages in LDS at most. */
+int32_t honu_key_compare(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_t *d_order_a /* optional */,
+                         const uint64_t *d_valid_a, uint64_t na,
+                         const uint64_t *d_obj_off_a, const uint64_t *d_objects_a,
+                         const uint8_t *d_sorted_b, const uint64_t *d_valid_b, uint64_t nb,
+                         honu_seek *d_out, uint32_t *d_peer /* optional */, uint64_t *d_counts /* optional */,
+                         void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
