@@ -4,6 +4,9 @@
 // iterator/cursor.go:31-38 makes of each bbolt value; the payloads a Put
 // hands over). One thread copies 10-20 GB/s; PCIe Gen5 x16 moves ~50 GB/s,
 // so large batches split their copies by bytes over a few threads.
+//
+// HIP-free (the standard library only), so tests/test_feed_host.py builds it
+// into a stand-alone program under the sanitizers.
 #pragma once
 
 #include <algorithm>
@@ -28,11 +31,10 @@ inline unsigned host_copy_threads() {
     return std::max(1u, std::min(8u, hw ? hw / 2 : 1u));
 }
 
-// Copies every job; with total >= kParallelCopyMin the byte space of the
-// jobs (in order) is cut into equal ranges, one per thread.
-inline void host_copy(const std::vector<HostCopy> &jobs, uint64_t total) {
-    const unsigned T = total >= kParallelCopyMin ? host_copy_threads() : 1;
-    if (T == 1) {
+// Copies every job over T threads: the byte space of the jobs (in order) is
+// cut into equal ranges, one per thread. total = the sum of the jobs' lengths.
+inline void host_copy_ranges(const std::vector<HostCopy> &jobs, uint64_t total, unsigned T) {
+    if (T <= 1) {
         for (const HostCopy &j : jobs)
             if (j.len) std::memcpy(j.dst, j.src, j.len);
         return;
@@ -51,6 +53,32 @@ inline void host_copy(const std::vector<HostCopy> &jobs, uint64_t total) {
     for (unsigned t = 1; t < T; t++) pool.emplace_back(run, total * t / T, total * (t + 1) / T);
     run(0, total / T);
     for (std::thread &th : pool) th.join();
+}
+
+// Copies every job; with total >= kParallelCopyMin over `threads` threads
+// (0: host_copy_threads()), below it on the calling thread.
+inline void host_copy(const std::vector<HostCopy> &jobs, uint64_t total, unsigned threads = 0) {
+    const unsigned T = total >= kParallelCopyMin ? (threads ? threads : host_copy_threads()) : 1;
+    host_copy_ranges(jobs, total, T);
+}
+
+// Equal-byte record ranges for T threads: record i takes need[i] of `bytes`
+// (their sum). Returns cuts c[0] = 0 <= c[1] <= ... <= c[m] = need.size(),
+// m <= T; thread j fills records [c[j], c[j + 1]).
+inline std::vector<uint64_t> record_cuts(const std::vector<uint64_t> &need, uint64_t bytes,
+                                         unsigned T) {
+    const uint64_t k = need.size();
+    std::vector<uint64_t> cuts{0};
+    uint64_t acc = 0, t = 1;
+    for (uint64_t i = 0; i < k && t < T; i++) {
+        acc += need[i];
+        if (acc >= bytes * t / T) {
+            cuts.push_back(i + 1);
+            t++;
+        }
+    }
+    cuts.push_back(k);
+    return cuts;
 }
 
 }  // namespace honu

@@ -76,6 +76,20 @@ class RecordFeed:
             _lib.check(st, "honu_feed_append")
         return st
 
+    def reserve(self, length: int) -> Optional[np.ndarray]:
+        """Reserve `length` bytes of pinned memory for the next record
+        (honu_feed_reserve) and return a writable view of them for the caller
+        to fill before submit(); None (HONU_ERR_CAPACITY) when the batch is full."""
+        err = _lib.I32(0)
+        p = self.lib.honu_feed_reserve(self.feed, length, C.byref(err))
+        if not p:
+            if err.value != 9:
+                _lib.check(err.value or -1, "honu_feed_reserve")
+            return None
+        if not length:
+            return np.zeros(0, np.uint8)
+        return np.frombuffer((C.c_uint8 * length).from_address(p), np.uint8)
+
     def append_batch(self, arena: np.ndarray, off: np.ndarray, first: int = 0):
         """Append records first.. of a CSR arena until the batch is full.
         Returns (status, records appended)."""
