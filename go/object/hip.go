@@ -21,6 +21,7 @@
 //	Cursor.Seek, Has, Exists  iterator/cursor.go:44-55, collection.go:47-65 -> (*Codec).SeekKeys, Has, Exists
 //	pid.Next, Tombstone       lamport/pid.go:10-15, metadata/collection.go:56-63 -> (*Codec).NextVersions
 //	lamport.Compare, two replicas  lamport/scalar.go:15-78, keys/keys.go:35-36 -> (*Codec).CompareKeys
+//	Drop "to free up space"   store.go:314-322, 399-404 -> (*Codec).ReclaimRecords
 package object
 
 /*
@@ -1335,6 +1336,99 @@ func (c *Codec) CompareKeys(mine, peer *KeyOrder) ([]Compared, CompareCounts, er
 		out[j] = Compared{Seek{uint32(r.pos), uint32(r.end), uint32(r.first), uint32(r.latest), uint32(r.flags)}, at[j]}
 	}
 	return out, counts, nil
+}
+
+// Reclaimed is what ReclaimRecords leaves on the device: the per-record state
+// of a store over Kept records, and the order of its column over their new
+// indices. Values and RecOff are a CSR records arena again; Keys, KeyStatus and
+// Info are set where the store's were given.
+type Reclaimed struct {
+	Kept   uint64   // the records that stay: n and nrec of the calls that follow, b_base of the next merge
+	Bytes  uint64   // the bytes of Values
+	Source []uint32 // per new record its old index, ascending: for per-record arrays of the caller's own
+
+	Order, Values, RecOff, Keys, KeyStatus, Info devBuf
+}
+
+func (r *Reclaimed) Free() {
+	for _, d := range []devBuf{r.Order, r.Values, r.RecOff, r.Keys, r.KeyStatus, r.Info} {
+		if d.p != nil {
+			d.free()
+		}
+	}
+}
+
+// ReclaimRecords frees the space of deleted records: Store.Drop exists "to free
+// up space in the database" (store.go:314-322), and after its DeleteBucket
+// bbolt "marks the pages as free" (store.go:399-404). o is the column's order
+// as SortKeys, MergeKeys or DeleteKeys left it; rec, recOff (nrec + 1 offsets)
+// and recBytes are the records arena on the device, keys, keyStatus and info
+// the per-record arrays beside it (each may be the zero devBuf). Every record
+// that one of the column's valid rows names stays, renumbered in ascending old
+// index, so arrival order survives; the others, the removed rows of the
+// deletes and the invalid rows of the batches, are freed. The column itself
+// stands: its first Kept rows with Reclaimed.Order are the new column. The
+// first call sizes (val_cap 0), the second copies into an arena of exactly
+// Bytes. The read of Kept is the one host round trip a caller needs before its
+// next MergeKeys, whose record base it is.
+//
+// UNCOMPILED, like the rest of this file. honu_key_reclaim is exercised on the
+// GPU from Python (tests/test_gpu_key_reclaim.py, tests/test_gpu_store_reclaim.py),
+// graph capture included.
+func (c *Codec) ReclaimRecords(o *KeyOrder, rec, recOff devBuf, nrec, recBytes uint64, keys, keyStatus, info devBuf) (out *Reclaimed, err error) {
+	n := o.n
+	out = &Reclaimed{}
+	out.Order, out.RecOff = device(uintptr(4*n)), device(uintptr(8*(nrec+1)))
+	if keys.p != nil {
+		out.Keys = device(uintptr(C.HONU_KEY_LEN * nrec))
+	}
+	if keyStatus.p != nil {
+		out.KeyStatus = device(uintptr(4 * nrec))
+	}
+	if info.p != nil {
+		out.Info = device(uintptr(uint64(C.honu_sizeof_record_info()) * nrec))
+	}
+	workBytes := uint64(C.honu_key_reclaim_workspace(C.uint64_t(nrec)))
+	work, dSource, dCounts := device(uintptr(workBytes)), device(uintptr(4*nrec)), device(16)
+	hSource, hCounts := pinned(uintptr(4*nrec)), pinned(16)
+	defer work.free()
+	defer dSource.free()
+	defer dCounts.free()
+	defer hSource.free()
+	defer hCounts.free()
+	reclaim := func(dValues devBuf, valCap uint64) C.int32_t {
+		return C.honu_key_reclaim(c.ctx, (*C.uint32_t)(o.order.p), (*C.uint64_t)(o.valid.p), C.uint64_t(n),
+			(*C.uint8_t)(keys.p), (*C.int32_t)(keyStatus.p), (*C.honu_record_info)(info.p),
+			(*C.uint8_t)(rec.p), (*C.uint64_t)(recOff.p), C.uint64_t(nrec), C.uint64_t(recBytes), 0,
+			(*C.uint32_t)(out.Order.p), nil, (*C.uint32_t)(dSource.p),
+			(*C.uint8_t)(out.Keys.p), (*C.int32_t)(out.KeyStatus.p), (*C.honu_record_info)(out.Info.p),
+			(*C.uint64_t)(out.RecOff.p), nil, (*C.uint8_t)(dValues.p), C.uint64_t(valCap),
+			(*C.uint64_t)(dCounts.p), (*C.uint64_t)(unsafe.Add(dCounts.p, 8)), work.p, C.uint64_t(workBytes), c.stream)
+	}
+	for _, s := range []C.int32_t{
+		reclaim(devBuf{}, 0), // sizes only
+		C.honu_memcpy_d2h(hCounts.p, dCounts.p, 16, c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_reclaim", s); err != nil {
+			out.Free()
+			return nil, err
+		}
+	}
+	out.Kept, out.Bytes = *(*uint64)(hCounts.p), *(*uint64)(unsafe.Add(hCounts.p, 8))
+	out.Values = device(uintptr(out.Bytes))
+	for _, s := range []C.int32_t{
+		reclaim(out.Values, out.Bytes),
+		C.honu_memcpy_d2h(hSource.p, dSource.p, C.uint64_t(4*out.Kept), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_reclaim", s); err != nil {
+			out.Free()
+			return nil, err
+		}
+	}
+	out.Source = append([]uint32(nil), unsafe.Slice((*uint32)(hSource.p), out.Kept)...)
+	return out, nil
 }
 
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&

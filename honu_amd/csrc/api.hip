@@ -373,6 +373,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "filter_tile")) *value = filter_tile();  // read only: list rows per workgroup of the filter
     else if (!strcmp(name, "compare_tile")) *value = compare_tile();    // read only: objects per workgroup of the compare
     else if (!strcmp(name, "compare_stage")) *value = compare_stage();  // read only: peer rows a workgroup of the compare stages in LDS
+    else if (!strcmp(name, "reclaim_tile")) *value = reclaim_tile();  // read only: records per workgroup of the reclaim
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -1019,6 +1020,47 @@ int32_t honu_key_compare(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_
     const uint32_t stage = (uint32_t)env_int("HONU_COMPARE_STAGE", (int)compare_stage());
     HIPCHK(launch_key_compare(d_sorted_a, d_order_a, d_valid_a, na, d_obj_off_a, d_objects_a, d_sorted_b, d_valid_b,
                               nb, stage, d_out, d_peer, d_counts, d_work, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the space a Drop frees: the records arena and the per-record arrays
+// compacted to the records the column still names (store.go:314-322, 399-404)
+// ---------------------------------------------------------------------------
+uint64_t honu_key_reclaim_workspace(uint64_t nrec) { return reclaim_workspace_bytes(nrec); }
+
+int32_t honu_key_reclaim(honu_ctx *ctx, const uint32_t *d_order, const uint64_t *d_valid, uint64_t n,
+                         const uint8_t *d_keys, const int32_t *d_key_status, const honu_record_info *d_info,
+                         const uint8_t *d_rec, const uint64_t *d_rec_off, uint64_t nrec, uint64_t rec_bytes,
+                         uint32_t flags, uint32_t *d_order_out, uint32_t *d_remap, uint32_t *d_source,
+                         uint8_t *d_keys_out, int32_t *d_key_status_out, honu_record_info *d_info_out,
+                         uint64_t *d_rec_off_out, int32_t *d_status, uint8_t *d_values, uint64_t val_cap,
+                         uint64_t *d_kept, uint64_t *d_val_total, void *d_work, uint64_t work_bytes,
+                         void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (n > 0xFFFFFFFFull || nrec > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
+    // the nrec + 1 lengths are scanned in place with the context's scan state, which covers max_records rows
+    if (nrec + 1 > ctx->max_n) return HONU_E_WORKSPACE;
+    if (flags) return arg_fail("unknown flag bits");
+    if (!d_valid || !d_kept || !d_val_total) return arg_fail("null d_valid, d_kept or d_val_total");
+    if (!d_rec_off || !d_rec_off_out || !d_source) return arg_fail("null record offsets or d_source");
+    if (n && (!d_order || !d_order_out)) return arg_fail("null order");
+    if ((rec_bytes && !d_rec) || (val_cap && !d_values)) return arg_fail("null arena of a size other than 0");
+    if (!d_keys != !d_keys_out || !d_key_status != !d_key_status_out || !d_info != !d_info_out)
+        return arg_fail("a per-record array and its output go together");
+    if (!aligned(d_order, 4) || !aligned(d_order_out, 4) || !aligned(d_remap, 4) || !aligned(d_source, 4) ||
+        !aligned(d_key_status, 4) || !aligned(d_key_status_out, 4) || !aligned(d_status, 4) ||
+        !aligned(d_valid, 8) || !aligned(d_kept, 8) || !aligned(d_val_total, 8) || !aligned(d_rec_off, 8) ||
+        !aligned(d_rec_off_out, 8) || !aligned(d_info, 8) || !aligned(d_info_out, 8))
+        return arg_fail("orders, remap, source and statuses 4-byte / counts, offsets and info 8-byte aligned");
+    const uint64_t need = reclaim_workspace_bytes(nrec);
+    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_reclaim_workspace(nrec)");
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_reclaim(copy_geom(ctx), d_order, d_valid, n, d_keys, d_key_status, d_info, d_rec, d_rec_off,
+                              nrec, rec_bytes, d_order_out, d_remap, d_source, d_keys_out, d_key_status_out,
+                              d_info_out, d_rec_off_out, d_status, d_values, val_cap, d_kept, d_val_total, d_work,
+                              ctx->scan, (hipStream_t)stream));
     return HONU_OK;
 }
 

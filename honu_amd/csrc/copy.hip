@@ -132,6 +132,37 @@ struct FetchSegments {
     }
 };
 
+// Segment j of honu_key_reclaim (reclaim.hip): new record j, logical start =
+// val_off[j] (the destination offset, the scanned lengths: n + 1 values, flat
+// from the kept count on), src = rec + rec_off[source[j]]. FetchSegments with
+// the record index from d_source: the place pass gave a slot a length other
+// than 0 only below the kept count, where source[j] is a checked index with
+// offsets in order inside the arena; a slot without a length (at or past the
+// kept count, where source holds nothing written, or a refused offset pair) is
+// not looked up in rec_off at all.
+struct ReclaimSegments {
+    const uint32_t *source;
+    const uint8_t *rec;
+    const uint64_t *rec_off;
+    const uint64_t *val_off;
+    uint8_t *values;
+    uint64_t val_cap;
+
+    HONU_DEV uint64_t start(uint64_t j) const { return val_off[j]; }
+    HONU_DEV uint64_t lo() const { return 0; }
+    HONU_DEV bool get(uint64_t j, uint64_t &len, const uint8_t *&src, uint8_t *&dst, uint64_t &skip) const {
+        skip = 0;
+        const uint64_t o0 = val_off[j], o1 = val_off[j + 1];  // with the record's index in one round trip
+        const uint32_t r = source[j];
+        len = o1 - o0;
+        // the records that fit are a prefix (the offsets are monotone); nothing is written at or past val_cap
+        const bool ok = len != 0 && o1 <= val_cap;
+        src = rec + (ok ? rec_off[r] : 0);
+        dst = values + o0;
+        return ok;
+    }
+};
+
 #define SMALL_SEG_WAVES_FACTOR 4
 // average segment bytes from which a launch uses 1 / SMALL_SEG_WAVES_FACTOR of
 // its waves
@@ -344,6 +375,16 @@ hipError_t launch_fetch_copy(const LaunchGeom &g, const honu_list_row *rows, uin
                              uint64_t val_cap, hipStream_t s) {
     if (n == 0) return hipSuccess;
     FetchSegments seg{rows, rec, rec_off, val_off, values, val_cap};
+    return launch_copy(g, seg, n, val_off + n, g.copy_tickets, s);
+}
+
+// n = nrec: segments [0, n), the total at val_off + n. As launch_fetch_copy:
+// the full grid however few records stay, the classes by total / n
+hipError_t launch_reclaim_copy(const LaunchGeom &g, const uint32_t *source, uint64_t n, const uint8_t *rec,
+                               const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
+                               uint64_t val_cap, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    ReclaimSegments seg{source, rec, rec_off, val_off, values, val_cap};
     return launch_copy(g, seg, n, val_off + n, g.copy_tickets, s);
 }
 

@@ -356,6 +356,26 @@ hipError_t launch_key_compare(const uint8_t *sa, const uint32_t *order_a, const 
                               const uint64_t *valid_b, uint64_t nb, uint32_t stage, honu_seek *out, uint32_t *peer,
                               uint64_t *counts, void *work, hipStream_t s);
 
+// reclaim.hip: the space a Drop frees (store.go:314-322, 399-404): the records a valid row of the column names,
+// renumbered in ascending old index, with their per-record arrays (keys, key_status, info: each null or given with
+// its output) and their bytes packed into a new CSR arena (rec_off_out: nrec + 1 values, the lengths scanned in
+// place through launch_scan, so nrec + 1 must not exceed the rows the context's scan state covers). n, nrec <=
+// 2^32 - 1. The workspace is the caller's (reclaim_workspace_bytes(nrec)); remap and status may be null. g: the
+// call's own copy geometry. The copy itself is launch_reclaim_copy (copy.hip), ReclaimSegments over the
+// byte-balanced engine
+uint32_t reclaim_tile();
+uint64_t reclaim_workspace_bytes(uint64_t nrec);
+hipError_t launch_key_reclaim(const LaunchGeom &g, const uint32_t *order, const uint64_t *valid, uint64_t n,
+                              const uint8_t *keys, const int32_t *key_status, const honu_record_info *info,
+                              const uint8_t *rec, const uint64_t *rec_off, uint64_t nrec, uint64_t rec_bytes,
+                              uint32_t *order_out, uint32_t *remap, uint32_t *source, uint8_t *keys_out,
+                              int32_t *key_status_out, honu_record_info *info_out, uint64_t *rec_off_out,
+                              int32_t *status, uint8_t *values, uint64_t val_cap, uint64_t *kept,
+                              uint64_t *val_total, void *work, const ScanState &S, hipStream_t s);
+hipError_t launch_reclaim_copy(const LaunchGeom &g, const uint32_t *source, uint64_t n, const uint8_t *rec,
+                               const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
+                               uint64_t val_cap, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -35,6 +35,10 @@ Codec.next_versions (honu_key_next). compare() is the host statement of what
 two replicas decide when they meet, which side holds the later version of an
 object under "latest writer wins" (lamport/scalar.go:15-24, 47-78), over two
 such lists; the batch form is Codec.compare_keys (honu_key_compare).
+reclaim() is the host statement of what a Drop is for, "to free up space in
+the database" (store.go:314-322, 399-404): the records that delete() and
+compact() took out of the list taken out of the records and renumbered; the
+batch form is Codec.reclaim_records (honu_key_reclaim).
 """
 from __future__ import annotations
 
@@ -464,6 +468,56 @@ def compare(a: Sequence[bytes], b: Sequence[bytes]) -> List[Compare]:
         out.append(Compare(pos, a1, flags | (SEEK_FOUND if pos < a1 else 0), peer))
         a0 = a1
     return out
+
+
+def reclaim(order: Sequence[int], valid: int, values: Sequence[bytes], keys: Optional[Sequence] = None,
+            statuses: Optional[Sequence] = None, info: Optional[Sequence] = None):
+    """The space a Drop frees: Store.Drop exists "to free up space in the
+    database" (store.go:314-322), and after the DeleteBucket behind it bbolt
+    "marks the pages as free" (store.go:399-404). delete() and compact() take
+    rows out of the sorted list; this takes the records they named out of
+    `values`, the list of records that `order` indexes (sort_keys' order: the
+    position of a sorted row -> the index of its record), and out of the
+    per-record lists beside it (`keys`, `statuses`, `info`, each optional).
+
+    A record r stays when order[p] == r for some p < v, v = min(valid,
+    len(order)): the rows at or past v are the removed rows of a delete or the
+    invalid rows of a batch, and the records only they name are freed. The
+    records that stay are renumbered 0 .. kept - 1 in ascending old index, so
+    arrival order survives, which merge()'s tie rule and compact() rest on.
+    Returns (order_out, remap, source, values_out, keys_out, statuses_out,
+    info_out):
+      order_out   len(order) entries: the new index of order[p] for p < v,
+                  SEEK_NONE for an index that names no record and for p >= v;
+      remap       per old record its new index, or SEEK_NONE when freed;
+      source      per new record its old index, ascending;
+      values_out  [bytes(values[r]) for r in source], copies;
+      keys_out, statuses_out, info_out  the lists given, gathered by source;
+                  None for a list not given.
+    An index repeated in order[:v] keeps its record once and both positions
+    get the same new index; a `valid` above len(order) is clamped; an index
+    that is negative or not below len(values) names no record. The first kept
+    rows of the sorted list stand as they are: with them, order_out[:v] and
+    values_out the state is what seek(), scan(), fetch(), filter(), next(),
+    compare(), delete() and merge() take. The batch form on the GPU is
+    Codec.reclaim_records (honu_key_reclaim in include/honu_codec.h), which
+    equals this."""
+    from .metadata import SEEK_NONE
+    n, nrec = len(order), len(values)
+    v = min(max(int(valid), 0), n)
+    named = {int(order[p]) for p in range(v)}
+    source = [r for r in range(nrec) if r in named]
+    remap = [SEEK_NONE] * nrec
+    for j, r in enumerate(source):
+        remap[r] = j
+    order_out = [remap[int(order[p])] if 0 <= int(order[p]) < nrec else SEEK_NONE for p in range(v)]
+    order_out += [SEEK_NONE] * (n - v)
+
+    def gather(rows):
+        return None if rows is None else [rows[r] for r in source]
+
+    return (order_out, remap, source, [bytes(values[r]) for r in source], gather(keys), gather(statuses),
+            gather(info))
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

@@ -561,6 +561,70 @@ class Codec:
         return (out[:20 * na].view(torch.int32).view(na, 5), peer[:4 * na].view(torch.int32) if want_peer else None,
                 counts[:64].view(torch.int64) if want_counts else None)
 
+    def reclaim_workspace(self, nrec: int):
+        """The workspace of reclaim_records for nrec records (honu_key_reclaim_workspace)."""
+        nbytes = int(self.lib.honu_key_reclaim_workspace(nrec))
+        return self._empty(nbytes), nbytes
+
+    def reclaim_records(self, order, valid, n: int, rec, rec_off, nrec: int, rec_bytes: int, val_cap: int,
+                        keys=None, key_status=None, info=None, want_remap: bool = False) -> "ReclaimResult":
+        """The space a Drop frees (store.go:314-322, 399-404): the records
+        arena (rec, rec_off uint64[nrec + 1], rec_bytes readable bytes) and
+        the per-record arrays beside it (`keys` 29 bytes, `key_status` int32,
+        `info` honu_record_info per record; each optional) compacted to the
+        records that the first min(valid, n) entries of `order` name (the
+        order and valid count of sort_keys, merge_keys or delete_keys),
+        renumbered in ascending old index, and the order rewritten to the new
+        indices. keys.reclaim is the host statement. Returns a ReclaimResult
+        of device tensors; nothing is read on the host. The records with
+        rec_off[j + 1] <= val_cap are copied, a prefix; a caller that reads
+        val_total > val_cap calls again with more room (val_cap 0 only sizes).
+        The new state has kept records and kept column rows: the caller reads
+        `kept` once, for the b_base of its next merge_keys."""
+        order_out = self._empty(4 * n)
+        remap = self._empty(4 * nrec) if want_remap else None
+        source, status = self._empty(4 * nrec), self._empty(4 * nrec)
+        keys_out = self._empty(29 * nrec) if keys is not None else None
+        key_status_out = self._empty(4 * nrec) if key_status is not None else None
+        info_out = self._empty(32 * nrec) if info is not None else None
+        off_out = self._empty(8 * (nrec + 1))
+        values = self._empty(val_cap) if val_cap else None
+        kept, val_total = self._empty(8), self._empty(8)
+        work, work_bytes = self.reclaim_workspace(nrec)
+        _lib.check(self.lib.honu_key_reclaim(
+            self.ctx, _lib.ptr(order), _lib.ptr(valid), n, _lib.ptr(keys), _lib.ptr(key_status), _lib.ptr(info),
+            _lib.ptr(rec), _lib.ptr(rec_off), nrec, rec_bytes, 0, _lib.ptr(order_out), _lib.ptr(remap),
+            _lib.ptr(source), _lib.ptr(keys_out), _lib.ptr(key_status_out), _lib.ptr(info_out), _lib.ptr(off_out),
+            _lib.ptr(status), _lib.ptr(values), val_cap, _lib.ptr(kept), _lib.ptr(val_total), _lib.ptr(work),
+            work_bytes, self.stream), "honu_key_reclaim")
+        torch = _torch()
+        i32 = lambda t, k: t[:4 * k].view(torch.int32)  # noqa: E731
+        return ReclaimResult(
+            order=i32(order_out, n), remap=i32(remap, nrec) if want_remap else None, source=i32(source, nrec),
+            values=values[:val_cap] if val_cap else None, rec_off=off_out[:8 * (nrec + 1)].view(torch.int64),
+            kept=kept[:8].view(torch.int64), val_total=val_total[:8].view(torch.int64), status=i32(status, nrec),
+            keys=keys_out[:29 * nrec] if keys is not None else None,
+            key_status=i32(key_status_out, nrec) if key_status is not None else None,
+            info=info_out[:32 * nrec] if info is not None else None)
+
+
+@dataclass
+class ReclaimResult:
+    """What Codec.reclaim_records returns, all on the device. The first `kept`
+    entries of source, status and the gathered arrays are written; order holds
+    n entries, remap nrec, rec_off nrec + 1 (flat at val_total from kept on)."""
+    order: object       # int32[n]: the new record index of each valid row, SEEK_NONE (-1) elsewhere
+    remap: object       # int32[nrec] or None: old index -> new index or SEEK_NONE
+    source: object      # int32[nrec]: new index -> old index
+    values: object      # uint8[val_cap] or None: the new arena
+    rec_off: object     # int64[nrec + 1]: the new offsets
+    kept: object        # int64[1]
+    val_total: object   # int64[1]: the bytes the kept records need
+    status: object      # int32[nrec]: OK, or INPUT for a record whose offsets are out of order or of the arena
+    keys: object        # uint8[29 nrec] or None
+    key_status: object  # int32[nrec] or None
+    info: object        # uint8[32 nrec] or None: honu_record_info rows, verbatim
+
 
 _default: Optional[Codec] = None
 

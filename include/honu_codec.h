@@ -26,7 +26,8 @@
  *   deleted objects not listed  collection.go:132-134, 97-101  honu_key_filter (stable compaction of the listed rows)
  *   pid.Next, Tombstone (batch) lamport/pid.go:10-15, collection.go:75-137  honu_key_next (the version each write writes)
  *   lamport.Compare (two columns) lamport/scalar.go:15-78, keys/keys.go:35-36  honu_key_compare (who is later, what to send, forks)
- *   lani.Encodable.Size()       lani/lani.go:9-12      (host only; Size() is a Grow hint, not bytes)
+ *   Drop "to free up space"     store.go:314-322, 399-404  honu_key_reclaim (the records arena compacted to the records the column names)
+ *   lani.Encodable.Size()       lani/lani.go:9-12     (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
  *   - Every pointer argument named d_* is DEVICE memory (hipMalloc / torch
@@ -1253,6 +1254,100 @@ int32_t honu_key_compare(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_
                          const uint64_t *d_obj_off_a, const uint64_t *d_objects_a,
                          const uint8_t *d_sorted_b, const uint64_t *d_valid_b, uint64_t nb,
                          honu_seek *d_out, uint32_t *d_peer /* optional */, uint64_t *d_counts /* optional */,
+                         void *d_work, uint64_t work_bytes, void *stream);
+
+/* Bytes of honu_key_reclaim's workspace for nrec records: the marks, the
+ * tiles' keep masks and counts and a remap. A multiple of 256, monotonic in
+ * nrec, 0 for nrec == 0, at most 8 nrec + 2^20; needs no device. */
+uint64_t honu_key_reclaim_workspace(uint64_t nrec);
+
+/* The space a Drop frees. Store.Drop exists "to free up space in the
+ * database" (store.go:314-322), and after the DeleteBucket behind it bbolt
+ * "marks the pages as free" (store.go:399-404). honu_key_delete compacts the
+ * 29-byte column alone; this call compacts what the column's d_order indexes:
+ * the records arena with its offsets, and the per-record arrays a resident
+ * store keeps beside it (the unsorted keys, their statuses, the
+ * honu_record_info rows), to the records the column still names, and rewrites
+ * the order to the new indices. honu_amd/keys.py reclaim() is the host
+ * statement; this call equals it.
+ * Inputs. d_order, d_valid and n are the column's order as honu_sort_keys,
+ * honu_key_merge or honu_key_delete wrote it: v = min(d_valid[0], n) is read
+ * on the device. The sorted column itself is not an argument: its first v rows
+ * stand as they are. d_rec, d_rec_off[nrec + 1] are the records arena (any
+ * byte alignment), rec_bytes its readable size. d_keys (29-byte rows, any
+ * byte alignment), d_key_status and d_info are optional, each indexed by
+ * record, nrec rows; each is given exactly when its output is.
+ * Kept records. Record r < nrec is kept when d_order[p] == r for some p < v.
+ * The kept records are renumbered 0 .. kept - 1 in ascending old index, new(r):
+ * a stable renumbering, so arrival order survives, on which b_base, the
+ * merge's tie rule and HONU_DELETE_SUPERSEDED rest. Records named only by
+ * rows at or past v are freed: the removed rows of a delete, the invalid rows
+ * of a batch.
+ * Outputs. d_kept[0] = kept. d_source[j], j < kept, is the old index of new
+ * record j (room for nrec): a caller gathers per-record arrays of its own with
+ * it. d_remap[r] (optional), every r < nrec, is new(r) or HONU_SEEK_NONE.
+ * d_order_out[p] is new(d_order[p]) for p < v, HONU_SEEK_NONE when d_order[p]
+ * >= nrec, and HONU_SEEK_NONE for v <= p < n: all n entries are written.
+ * d_keys_out row j is the 29 bytes of d_keys row d_source[j];
+ * d_key_status_out[j] and d_info_out[j] likewise, the info row verbatim, so
+ * its data_off stays relative to the batch it was decoded from.
+ * Lengths follow honu_key_fetch: with r = d_source[j], a = d_rec_off[r] and b
+ * = d_rec_off[r + 1] give length b - a and d_status[j] (optional, room for
+ * nrec) = HONU_OK when a <= b <= rec_bytes, else length 0 and HONU_ERR_INPUT.
+ * d_rec_off_out[0, nrec] is the exclusive scan of the lengths, the entries at
+ * or past kept counting 0: flat at the total from kept on, and d_val_total[0]
+ * is that total. New record j is copied to d_values + d_rec_off_out[j] exactly
+ * when its length is not 0 and d_rec_off_out[j + 1] <= val_cap: the fetch's
+ * prefix rule, and a caller that reads d_val_total[0] > val_cap re-issues with
+ * more room. d_values may be NULL only with val_cap == 0: a sizing call.
+ * The write set is exactly d_kept[0], d_val_total[0], d_order_out[0, n),
+ * d_remap[0, nrec), d_source[0, kept), rows [0, kept) of the three gathered
+ * arrays, d_status[0, kept), d_rec_off_out[0, nrec + 1) and the bytes of the
+ * copied records, besides the workspace; the outputs must not overlap the
+ * inputs. With nrec == 0 only the two counts (0), d_rec_off_out[0] = 0 and
+ * d_order_out[0, n) (all HONU_SEEK_NONE) are written.
+ * Garbage in. An index repeated in d_order[0, v) keeps its record once, and
+ * both positions get the same new index; a count above n is clamped; an index
+ * not below nrec never reads d_rec_off or a per-record row. No record byte
+ * outside [0, rec_bytes) is read and no byte outside the write set is written
+ * (the copy loads whole aligned 16-byte blocks that hold at least one byte of
+ * a record it copies, as every payload copy does).
+ * What the result is fit for. With n' = nrec' = kept (the column's first kept
+ * rows and d_order_out's first kept entries; after a delete, v == kept of that
+ * delete when every kept row names a distinct record), the new state is fit
+ * for honu_key_seek, honu_key_objects, honu_key_list, honu_key_fetch,
+ * honu_key_filter, honu_key_next, honu_key_compare, a further honu_key_delete
+ * and honu_key_merge. A merge after a reclaim needs b_base = kept, and b_base
+ * is a host argument: one read of d_kept[0] follows a reclaim, as a caller
+ * reads a batch's byte total to size its arena.
+ * d_work is honu_key_reclaim_workspace(nrec) bytes, 256-byte aligned (unused,
+ * and NULL allowed, when that is 0). The tiles' counts and the nrec + 1
+ * lengths are summed by the context's scan, whose state covers max_records
+ * rows, so one context serves one stream at a time, as for honu_key_fetch;
+ * the copy takes a line of the context's copy counters like every payload
+ * copy. Asynchronous on `stream`, no host synchronisation, no allocation; the
+ * grids are sized from n and nrec; replays from a captured graph, also after
+ * d_valid and d_order were changed on the device between replays.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for n or nrec above 2^32 -
+ * 1, or for nrec + 1 above honu_ctx_max_records (honu_key_fetch refuses cap +
+ * 1 the same way); HONU_E_ARG for a NULL ctx, d_valid, d_kept, d_val_total,
+ * d_rec_off, d_rec_off_out or d_source, a NULL d_order or d_order_out with n >
+ * 0, a NULL d_rec with rec_bytes > 0, a NULL d_values with val_cap > 0, an
+ * optional input without its output or the output without its input, flags
+ * other than 0, work_bytes below honu_key_reclaim_workspace(nrec), a NULL or
+ * misaligned (256) workspace when that size is not 0, or a misaligned pointer
+ * (4 bytes: the orders, d_remap, d_source, the statuses; 8 bytes: the counts,
+ * the offsets, the info rows).
+ * The get-only param "reclaim_tile" is the records one workgroup takes. */
+int32_t honu_key_reclaim(honu_ctx *ctx, const uint32_t *d_order, const uint64_t *d_valid, uint64_t n,
+                         const uint8_t *d_keys /* optional */, const int32_t *d_key_status /* optional */,
+                         const honu_record_info *d_info /* optional */,
+                         const uint8_t *d_rec, const uint64_t *d_rec_off, uint64_t nrec, uint64_t rec_bytes,
+                         uint32_t flags,
+                         uint32_t *d_order_out, uint32_t *d_remap /* optional */, uint32_t *d_source,
+                         uint8_t *d_keys_out, int32_t *d_key_status_out, honu_record_info *d_info_out,
+                         uint64_t *d_rec_off_out, int32_t *d_status /* optional */,
+                         uint8_t *d_values, uint64_t val_cap, uint64_t *d_kept, uint64_t *d_val_total,
                          void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
