@@ -84,6 +84,18 @@ static int32_t arg_fail(const char *what) {
 
 static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
+// the caller's workspace against the `need` bytes that fn_of_arg ("honu_x_workspace(n)") returns: no
+// smaller, and non-null and 256-byte aligned when any are needed; 0 or the refusal
+static int32_t work_args(uint64_t need, const void *d_work, uint64_t work_bytes, const char *fn_of_arg) {
+    if (work_bytes < need) {
+        char what[128];
+        snprintf(what, sizeof what, "workspace smaller than %s", fn_of_arg);
+        return arg_fail(what);
+    }
+    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    return HONU_OK;
+}
+
 // record_variant 5 runs the batch entries through the split kernels of
 // variant 0, 6 through the fused decode at every size; variant 0 picks by size
 #define FUSED_DECODE_MIN_RECORDS (48ull << 10)
@@ -751,7 +763,8 @@ int32_t honu_decode_keys(honu_ctx *ctx, const honu_meta *d_meta, const honu_reco
 // ---------------------------------------------------------------------------
 uint64_t honu_sort_keys_workspace(uint64_t n) { return sort_workspace_bytes(n); }
 
-// the checks the two calls share; 0 or the refusal
+// the checks the two calls share; 0 or the refusal. (Not work_args: these calls look at the pointer first,
+// whatever n, and which error a doubly wrong call reports is behaviour.)
 static int32_t sort_args(honu_ctx *ctx, uint64_t n, const void *d_work, uint64_t work_bytes) {
     if (!ctx) return arg_fail("ctx");
     if (n > ctx->max_n || n > 0xFFFFFFFFull) return HONU_E_WORKSPACE;
@@ -856,9 +869,8 @@ int32_t honu_key_delete(honu_ctx *ctx, const uint8_t *d_sorted, const uint32_t *
     if (!aligned(d_order, 4) || !aligned(d_order_out, 4) || !aligned(d_valid, 8) || !aligned(d_valid_del, 8) ||
         !aligned(d_valid_out, 8) || !aligned(d_removed, 8))
         return arg_fail("orders 4-byte / counts 8-byte aligned");
-    const uint64_t need = delete_workspace_bytes(n);
-    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_delete_workspace(n)");
-    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    const int32_t st = work_args(delete_workspace_bytes(n), d_work, work_bytes, "honu_key_delete_workspace(n)");
+    if (st) return st;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_delete(d_sorted, d_order, d_valid, n, d_del, d_valid_del, m, probe_len, flags, d_sorted_out,
                              d_order_out, d_valid_out, d_removed, d_work, ctx->scan, (hipStream_t)stream));
@@ -949,9 +961,8 @@ int32_t honu_key_filter(honu_ctx *ctx, const honu_list_row *d_rows, const uint8_
         !aligned(d_obj_off, 8) || !aligned(d_objects, 8) || !aligned(d_info, 8) || !aligned(d_range_off_out, 8) ||
         !aligned(d_total_out, 8) || !aligned(d_rows, 16) || !aligned(d_rows_out, 16))
         return arg_fail("latest 4-byte / counts, offsets and info 8-byte / rows 16-byte aligned");
-    const uint64_t need = filter_workspace_bytes(cap);
-    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_filter_workspace(cap)");
-    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    const int32_t st = work_args(filter_workspace_bytes(cap), d_work, work_bytes, "honu_key_filter_workspace(cap)");
+    if (st) return st;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_filter(d_rows, d_keys, d_range_off, m, d_total, cap, flags, d_valid, n, d_obj_off, d_latest,
                              d_objects, d_info, d_rows_out, d_keys_out, d_range_off_out, d_total_out, d_work,
@@ -982,9 +993,8 @@ int32_t honu_key_next(honu_ctx *ctx, const uint8_t *d_sorted, const uint64_t *d_
     if (!aligned(d_order, 4) || !aligned(d_req_status, 4) || !aligned(d_key_status, 4) || !aligned(d_out, 8) ||
         !aligned(d_valid, 8) || !aligned(d_info, 8) || !aligned(d_meta, 8))
         return arg_fail("order and statuses 4-byte / d_out, valid count, record info and rows 8-byte aligned");
-    const uint64_t need = next_workspace_bytes(m);
-    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_next_workspace(m)");
-    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    const int32_t st = work_args(next_workspace_bytes(m), d_work, work_bytes, "honu_key_next_workspace(m)");
+    if (st) return st;
     if (m == 0) return HONU_OK;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_next(d_sorted, d_valid, n, d_order, d_info, d_requests, d_req_status, m, op, pid, region, now,
@@ -1012,9 +1022,8 @@ int32_t honu_key_compare(honu_ctx *ctx, const uint8_t *d_sorted_a, const uint32_
     if (!aligned(d_out, 4) || !aligned(d_peer, 4) || !aligned(d_order_a, 4) || !aligned(d_counts, 8) ||
         !aligned(d_valid_a, 8) || !aligned(d_valid_b, 8) || !aligned(d_obj_off_a, 8) || !aligned(d_objects_a, 8))
         return arg_fail("rows, peer and order 4-byte / counts and offsets 8-byte aligned");
-    const uint64_t need = compare_workspace_bytes(na);
-    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_compare_workspace(na)");
-    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    const int32_t st = work_args(compare_workspace_bytes(na), d_work, work_bytes, "honu_key_compare_workspace(na)");
+    if (st) return st;
     HIPCHK(hipSetDevice(ctx->device));
     // (make ab: HONU_COMPARE_STAGE below compare_stage sends more tiles down the unstaged path, 0 all of them)
     const uint32_t stage = (uint32_t)env_int("HONU_COMPARE_STAGE", (int)compare_stage());
@@ -1053,9 +1062,9 @@ int32_t honu_key_reclaim(honu_ctx *ctx, const uint32_t *d_order, const uint64_t 
         !aligned(d_valid, 8) || !aligned(d_kept, 8) || !aligned(d_val_total, 8) || !aligned(d_rec_off, 8) ||
         !aligned(d_rec_off_out, 8) || !aligned(d_info, 8) || !aligned(d_info_out, 8))
         return arg_fail("orders, remap, source and statuses 4-byte / counts, offsets and info 8-byte aligned");
-    const uint64_t need = reclaim_workspace_bytes(nrec);
-    if (work_bytes < need) return arg_fail("workspace smaller than honu_key_reclaim_workspace(nrec)");
-    if (need && (!d_work || !aligned(d_work, 256))) return arg_fail("workspace must be non-null and 256-byte aligned");
+    const int32_t st =
+        work_args(reclaim_workspace_bytes(nrec), d_work, work_bytes, "honu_key_reclaim_workspace(nrec)");
+    if (st) return st;
     HIPCHK(hipSetDevice(ctx->device));
     HIPCHK(launch_key_reclaim(copy_geom(ctx), d_order, d_valid, n, d_keys, d_key_status, d_info, d_rec, d_rec_off,
                               nrec, rec_bytes, d_order_out, d_remap, d_source, d_keys_out, d_key_status_out,

@@ -18,12 +18,11 @@
 // Two launches:
 //   compare  a workgroup per COMPARE_TILE consecutive objects, a thread per
 //            object (the grid comes from na; a workgroup past `objects` leaves
-//            at once). The tile's objects ascend, so the rows of B that any of
-//            them can match are one range: its two ends are found once per
-//            workgroup, a wave each (wave_bound over the 17-byte mask), and the
-//            range is staged packed in LDS (keycol.h's 9-word row) when it has
-//            no more than `stage` rows (COMPARE_STAGE); a longer one is searched
-//            in global memory inside the bracket. A thread then takes both
+//            at once). The rows of B that any of the tile's objects can match
+//            are one range (keycol.h's peer_range over the 17-byte mask),
+//            staged as whole keys in LDS when it has no more than `stage` rows
+//            (COMPARE_STAGE) and masked on use; a longer one is searched in
+//            global memory inside the range. A thread then takes both
 //            bounds of its prefix in the range (seek_bounds), compares the full
 //            packed keys, bisects [a0, a1 - 1) when it is ahead (thread_bound),
 //            and tests the ancestor row. The tile's class counts, a ballot per
@@ -45,7 +44,6 @@ constexpr uint32_t COMPARE_STAGE = 1024;       // rows of B a workgroup stages
 // of 256 objects whose peer holds up to four versions of each stays on the staged path
 constexpr uint32_t COMPARE_CLASSES = 5;      // only mine, later and the peer has it, earlier, equal, forks
 constexpr uint32_t COMPARE_PART_WORDS = 8;   // a tile's counts in the workspace: the classes, then zeros
-static_assert(HONU_WAVES_PER_BLOCK >= 2, "a wave for each end of the bracket");
 static_assert(COMPARE_PART_WORDS >= COMPARE_CLASSES && COMPARE_PART_WORDS <= HONU_WAVE, "a lane per word");
 
 uint32_t compare_tile() { return COMPARE_TILE; }
@@ -78,7 +76,6 @@ HONU_DEV void compare_object(const CompareArgs &C, uint32_t j, uint32_t va, uint
 __global__ __launch_bounds__(HONU_BLOCK) void k_compare(CompareArgs C, SeekMask M, honu_seek *__restrict__ out,
                                                          uint32_t *__restrict__ peer, uint32_t *__restrict__ part) {
     __shared__ uint32_t rows[COMPARE_STAGE * KEY_ROW_WORDS];
-    __shared__ uint32_t range[2];
     __shared__ uint32_t cnt[HONU_WAVES_PER_BLOCK][COMPARE_PART_WORDS];
     const uint32_t objects = valid_rows(C.objects, C.na);
     const uint32_t j0 = blockIdx.x * COMPARE_TILE;  // below na
@@ -87,40 +84,17 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_compare(CompareArgs C, SeekMask 
     const uint32_t va = valid_rows(C.valid_a, C.na), vb = C.nb ? valid_rows(C.valid_b, C.nb) : 0;
     const uint32_t wv = wave_in_block(), lane = lane_id();
 
-    // the rows [lo, hi) of B that an object of the tile can match
-    uint32_t lo = 0, hi = 0;
-    if (va && vb) {  // (block-uniform)
-        if (threadIdx.x < 2 * HONU_WAVE) {
-            uint32_t a0, a1, k[SORT_KEY_WORDS];
-            compare_object(C, wv ? j0 + len - 1 : j0, va, a0, a1);
+    // the rows of B that an object of the tile can match, staged as their whole keys
+    const auto R = peer_range(
+        [&](bool last, uint32_t k[SORT_KEY_WORDS]) {  // the latest key of the tile's first or last object
+            uint32_t a0, a1;
+            compare_object(C, last ? j0 + len - 1 : j0, va, a0, a1);
             load_masked(C.a + (uint64_t)HONU_KEY_LEN * (a1 ? a1 - 1 : 0), M, k);
-            const bool upper = wv != 0;
-            const uint32_t b = wave_bound(0, vb, [&](uint32_t mid) {
-                uint32_t d[SORT_KEY_WORDS];
-                load_masked(C.b + (uint64_t)HONU_KEY_LEN * mid, M, d);
-                return packed_before(d, k, upper);
-            });
-            if (lane == 0) range[wv] = b;
-        }
-        __syncthreads();
-        lo = range[0];                       // <= vb
-        hi = range[1] < lo ? lo : range[1];  // <= vb (lo <= hi over sorted columns)
-    }
-    const uint32_t dn = hi - lo;
-    const bool staged = dn <= C.stage;
-    if (dn && staged) {  // (block-uniform)
-        for (uint32_t r = threadIdx.x; r < dn; r += HONU_BLOCK) {
-            uint32_t d[SORT_KEY_WORDS];
-            pack_key(C.b + (uint64_t)HONU_KEY_LEN * (lo + r), true, d);
-            lds_row_store(rows, r, d);
-        }
-        __syncthreads();
-    }
-    // row `at` of the range, the whole key
-    auto peer_key = [&](uint32_t at, uint32_t d[SORT_KEY_WORDS]) {
-        if (staged) lds_row_load(rows, at, d);
-        else pack_key(C.b + (uint64_t)HONU_KEY_LEN * (lo + at), true, d);
-    };
+        },
+        C.b, va ? vb : 0, M,
+        [&](uint32_t at, uint32_t d[SORT_KEY_WORDS]) { pack_key(C.b + (uint64_t)HONU_KEY_LEN * at, true, d); }, C.stage,
+        rows);
+    const uint32_t lo = R.lo, dn = R.dn;
 
     const uint32_t t = threadIdx.x;
     uint32_t cls = COMPARE_CLASSES;  // none: a thread past the tile
@@ -139,7 +113,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_compare(CompareArgs C, SeekMask 
             if (dn)
                 seek_bounds(
                     [&](uint32_t at, uint32_t x[SORT_KEY_WORDS]) {
-                        peer_key(at, x);
+                        R.load(at, x);
 #pragma unroll
                         for (int i = 0; i < SORT_KEY_WORDS; i++) x[i] &= M.w[i];
                     },
@@ -147,7 +121,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_compare(CompareArgs C, SeekMask 
             if (b0 < b1) {
                 flags |= HONU_CMP_PEER_HAS;
                 at_peer = lo + b1 - 1;
-                peer_key(b1 - 1, pb);
+                R.load(b1 - 1, pb);
                 const int c = cmp_packed(K, pb);
                 bool ancestor = true;
                 if (c > 0) {  // the first row above the peer's latest: K is above it, so at most a1 - 1
@@ -165,10 +139,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_compare(CompareArgs C, SeekMask 
                 } else if (c < 0) {  // K among the peer's rows: its lower bound in [b0, b1 - 1), then equality
                     pos = a1;
                     const uint32_t at = thread_bound(b0, b1 - 1, [&](uint32_t mid) {
-                        peer_key(mid, d);
+                        R.load(mid, d);
                         return packed_before(d, K, false);
                     });
-                    peer_key(at, d);  // (at <= b1 - 1)
+                    R.load(at, d);  // (at <= b1 - 1)
                     ancestor = packed_same(d, K);
                     flags |= HONU_CMP_EARLIER;
                     cls = 2;

@@ -1,7 +1,9 @@
 // keycol.h — what the kernels over the ordered key column share: the sort
 // (sort.hip), the seek (seek.hip), the merge (merge.hip), the delete
 // (delete.hip), the list (list.hip), the filter (filter.hip), the version
-// assignment (next.hip) and the comparison of two columns (compare.hip).
+// assignment (next.hip), the comparison of two columns (compare.hip) and the
+// reclaim (reclaim.hip). The compaction that delete, filter and reclaim share
+// is compact.h's.
 //   the packed key  a 29-byte key as 32 bytes read as eight big-endian words,
 //                   byte 0 the validity (0 valid, 1 not), bytes 1-29 the key,
 //                   bytes 30-31 zero. An unsigned compare of the words from
@@ -9,7 +11,10 @@
 //   rows            a key moved as its bytes, the counts and indices read on
 //                   the device clamped to the rows, the 9-word row in LDS;
 //   searches        the leading positions of a bracket that say yes to a
-//                   predicate, by a wave (64 mids per step) or by a thread.
+//                   predicate, by a wave (64 mids per step) or by a thread;
+//   the peer range  the rows of a second sorted column that a workgroup's
+//                   tile can match, found once per workgroup and staged in
+//                   LDS when short (peer_range: delete.hip, compare.hip).
 #pragma once
 
 #include "common.h"
@@ -172,6 +177,64 @@ template <typename Yes> HONU_DEV uint32_t thread_bound(uint32_t lo, uint32_t hi,
         else hi = mid;
     }
     return lo;
+}
+
+// The rows of a sorted peer column that any row of a workgroup's tile can
+// match (delete.hip: the delete list; compare.hip: the peer's column): the
+// tile's rows ascend, so they are one range [lo, lo + dn), and it is staged in
+// the caller's LDS rows (the 9-word row) when it has no more than `stage` of
+// them. load gives row `at` of the range in pack's form, out of LDS when it
+// is staged and through pack when it is not.
+template <typename Pack> struct PeerRange {
+    uint32_t lo, dn;
+    bool staged;  // (block-uniform)
+    const uint32_t *rows;
+    Pack pack;
+    HONU_DEV void load(uint32_t at, uint32_t d[SORT_KEY_WORDS]) const {
+        if (staged) lds_row_load(rows, at, d);
+        else pack(lo + at, d);
+    }
+};
+
+// By the whole workgroup, with a barrier after each of its two steps when the
+// step runs. The two ends are found once, a wave each (wave_bound over the
+// masked keys of the peer's first n rows): end_key(last, k) gives the masked
+// key of the tile's first row, or of its last, and n == 0 says there is none.
+// pack(at, d) gives row `at` of the peer as it is staged, `rows` holds `stage`
+// rows at least.
+static_assert(HONU_WAVES_PER_BLOCK >= 2, "a wave for each end of the range");
+template <typename EndKey, typename Pack>
+HONU_DEV PeerRange<Pack> peer_range(EndKey end_key, const uint8_t *__restrict__ peer, uint32_t n, const SeekMask &M,
+                                    Pack pack, uint32_t stage, uint32_t *rows) {
+    __shared__ uint32_t range[2];
+    const uint32_t wv = wave_in_block(), lane = lane_id();
+    uint32_t lo = 0, hi = 0;
+    if (n) {  // (block-uniform)
+        if (threadIdx.x < 2 * HONU_WAVE) {
+            uint32_t k[SORT_KEY_WORDS];
+            end_key(wv != 0, k);
+            const uint32_t b = wave_bound(0, n, [&](uint32_t mid) {  // wave 0 the lower bound, wave 1 the upper
+                uint32_t d[SORT_KEY_WORDS];
+                load_masked(peer + (uint64_t)HONU_KEY_LEN * mid, M, d);
+                return packed_before(d, k, wv != 0);
+            });
+            if (lane == 0) range[wv] = b;
+        }
+        __syncthreads();
+        lo = range[0];                       // <= n
+        hi = range[1] < lo ? lo : range[1];  // <= n (lo <= hi over sorted columns)
+    }
+    const uint32_t dn = hi - lo;
+    const bool staged = dn <= stage;
+    if (dn && staged) {  // (block-uniform)
+        for (uint32_t r = threadIdx.x; r < dn; r += HONU_BLOCK) {
+            uint32_t d[SORT_KEY_WORDS];
+            pack(lo + r, d);
+            lds_row_store(rows, r, d);
+        }
+        __syncthreads();
+    }
+    return {lo, dn, staged, rows, pack};
 }
 
 // Both bounds of a probe by one thread (seek.hip, next.hip): the lower bound's

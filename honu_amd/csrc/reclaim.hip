@@ -6,22 +6,21 @@
 // renumbered 0 .. kept - 1 in ascending old index, so arrival order survives,
 // and the column's order is rewritten to the new indices.
 //
-// delete.hip's mark / scan / place over records instead of column rows, then
-// fetch.hip's lengths / scan / copy over the records that stay:
+// compact.h's mark / scan / place over records, a workgroup per RECLAIM_TILE
+// of them, then fetch.hip's lengths / scan / copy over the records that stay:
 //   clear    hipMemsetAsync over the marks, a byte per record;
 //   mark     a thread per column position p < v: marks[d_order[p]] = 1 when the
 //            index is below nrec. Plain stores: the stores that race to one
 //            mark all store the same byte;
-//   count    a workgroup per RECLAIM_TILE records: a ballot per 64 records
-//            and the tile's kept count;
+//   count    the compaction's mark: a record stays when its mark is set;
 //   scan     launch_scan over the tiles' counts, the total to d_kept;
-//   place    a kept record's new index j is kept_before_tile + the popcount
-//            of the masks below it: d_remap[r] = j, d_source[j] = r, the
-//            record's key (copy_key), key status and info row to row j, its
-//            checked length to d_rec_off_out[j] and its status to d_status[j].
-//            A freed record r writes HONU_SEEK_NONE to d_remap[r] and the zero
-//            length of slot kept + (r - kept_before_r), so the slots [kept,
-//            nrec) are all written; slot nrec is the first thread's;
+//   place    a kept record's new index j is its rank: d_remap[r] = j,
+//            d_source[j] = r, the record's key (copy_key), key status and info
+//            row to row j, its checked length to d_rec_off_out[j] and its
+//            status to d_status[j]. A freed record r writes HONU_SEEK_NONE to
+//            d_remap[r] and the zero length of slot kept + (r - kept_before_r),
+//            so the slots [kept, nrec) are all written; slot nrec is the first
+//            thread's;
 //   scan     launch_scan in place over the nrec + 1 lengths, the total to
 //            d_val_total;
 //   renumber a thread per column position: d_order_out[p] = remap[d_order[p]]
@@ -29,51 +28,36 @@
 //   copy     k_copy_segments<ReclaimSegments> (copy.hip) over nrec segments,
 //            the new arena its logical byte space.
 // The remap goes to d_remap or, without one, to the workspace. The kernels
-// here have no atomics, no spin-wait and no state outside the launch;
+// here have no atomics, no spin-wait and no state outside the launch either;
 // launch_scan is the only step in which workgroups depend on each other. The
 // grids come from n and nrec, never from a count on the device. An index read
 // from d_order is checked against nrec before anything is read with it, and
 // every offset pair against rec_bytes before its length counts.
-#include "kernels.h"
+#include "compact.h"
 #include "keycol.h"
 
 namespace honu {
 
-constexpr uint32_t RECLAIM_TILE = 1024;                                    // records per workgroup
-constexpr uint32_t RECLAIM_WORDS = RECLAIM_TILE / HONU_WAVE;               // ballots per tile
-constexpr uint32_t RECLAIM_ROUNDS = RECLAIM_WORDS / HONU_WAVES_PER_BLOCK;  // ballots per wave
-static_assert(RECLAIM_TILE % (HONU_WAVE * HONU_WAVES_PER_BLOCK) == 0, "a wave takes whole ballots");
-static_assert(RECLAIM_WORDS <= HONU_BLOCK, "a thread per ballot in the place kernel");
+constexpr uint32_t RECLAIM_TILE = 1024;  // records per workgroup
 
 uint32_t reclaim_tile() { return RECLAIM_TILE; }
-static uint64_t reclaim_tiles(uint64_t nrec) { return (nrec + RECLAIM_TILE - 1) / RECLAIM_TILE; }
 
-// the marks (a byte per record), the keep masks (RECLAIM_WORDS words per tile), the kept counts (a word
-// per tile), then the remap of a call without d_remap (a word per record)
+// the marks (a byte per record), the compaction's masks and counts, then the remap of a call without
+// d_remap (a word per record)
 uint64_t reclaim_workspace_bytes(uint64_t nrec) {
-    const uint64_t tiles = reclaim_tiles(nrec);
-    return up256(nrec) + up256(8 * RECLAIM_WORDS * tiles) + up256(8 * tiles) + up256(4 * nrec);
+    return up256(nrec) + compact_workspace_bytes<RECLAIM_TILE>(nrec) + up256(4 * nrec);
 }
 
 struct ReclaimWork {
     uint8_t *marks;
-    uint64_t *mask;
-    uint64_t *kept;
+    CompactWork c;
     uint32_t *remap;
 };
 
 static ReclaimWork reclaim_carve(void *work, uint64_t nrec) {
-    const uint64_t tiles = reclaim_tiles(nrec);
-    ReclaimWork w;
-    uint8_t *at = (uint8_t *)work;
-    w.marks = at;
-    at += up256(nrec);
-    w.mask = (uint64_t *)at;
-    at += up256(8 * RECLAIM_WORDS * tiles);
-    w.kept = (uint64_t *)at;
-    at += up256(8 * tiles);
-    w.remap = (uint32_t *)at;
-    return w;
+    uint8_t *at = (uint8_t *)work + up256(nrec);
+    return {(uint8_t *)work, compact_carve<RECLAIM_TILE>(at, nrec),
+            (uint32_t *)(at + compact_workspace_bytes<RECLAIM_TILE>(nrec))};
 }
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_reclaim_mark(const uint32_t *__restrict__ order,
@@ -86,27 +70,10 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_reclaim_mark(const uint32_t *__r
 }
 
 __global__ __launch_bounds__(HONU_BLOCK) void k_reclaim_count(uint32_t nrec, ReclaimWork W) {
-    __shared__ uint32_t cnt[HONU_WAVES_PER_BLOCK];
     const uint32_t r0 = blockIdx.x * RECLAIM_TILE;  // below nrec
     const uint32_t len = nrec - r0 < RECLAIM_TILE ? nrec - r0 : RECLAIM_TILE;
-    const uint32_t wv = wave_in_block(), lane = lane_id();
-    uint32_t kept = 0;
-    for (uint32_t q = 0; q < RECLAIM_ROUNDS; q++) {
-        const uint32_t j = q * HONU_WAVES_PER_BLOCK + wv;  // the tile's ballot: records [64 j, 64 j + 64)
-        const uint32_t t = j * HONU_WAVE + lane;
-        const bool keep = t < len && W.marks[(uint64_t)r0 + t] != 0;
-        const uint64_t bits = __ballot(keep);
-        if (lane == 0) W.mask[(uint64_t)blockIdx.x * RECLAIM_WORDS + j] = bits;
-        kept += (uint32_t)__popcll(bits);
-    }
-    if (lane == 0) cnt[wv] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < HONU_WAVES_PER_BLOCK; w++) sum += cnt[w];
-        W.kept[blockIdx.x] = sum;
-    }
+    compact_mark<RECLAIM_TILE>(W.c, blockIdx.x,
+                               [&](uint32_t, uint32_t t) { return t < len && W.marks[(uint64_t)r0 + t] != 0; });
 }
 
 struct ReclaimArrays {
@@ -123,36 +90,25 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_reclaim_place(
     const uint64_t *__restrict__ rec_off, uint32_t nrec, uint64_t rec_bytes, ReclaimArrays A,
     const uint64_t *__restrict__ kept_total, uint32_t *__restrict__ remap, uint32_t *__restrict__ source,
     uint64_t *__restrict__ len_out, int32_t *__restrict__ status, ReclaimWork W) {
-    __shared__ uint64_t msk[RECLAIM_WORDS];
-    __shared__ uint32_t pre[RECLAIM_WORDS];  // records kept in the tile's ballots before ballot j
     const uint64_t kept = *kept_total < nrec ? *kept_total : nrec;
     if (blockIdx.x == 0 && threadIdx.x == 0) len_out[nrec] = 0;
     const uint32_t r0 = blockIdx.x * RECLAIM_TILE;  // below nrec
     const uint32_t len = nrec - r0 < RECLAIM_TILE ? nrec - r0 : RECLAIM_TILE;
-    if (threadIdx.x < RECLAIM_WORDS) msk[threadIdx.x] = W.mask[(uint64_t)blockIdx.x * RECLAIM_WORDS + threadIdx.x];
-    __syncthreads();
-    if (threadIdx.x < RECLAIM_WORDS) {
-        uint32_t s = 0;
-        for (uint32_t j = 0; j < threadIdx.x; j++) s += (uint32_t)__popcll(msk[j]);
-        pre[threadIdx.x] = s;
-    }
-    __syncthreads();
-    const uint64_t base = W.kept[blockIdx.x];
+    const CompactRanks K = compact_ranks<RECLAIM_TILE>(W.c, blockIdx.x);
     const uint32_t wv = wave_in_block(), lane = lane_id();
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0;
-    for (uint32_t q = 0; q < RECLAIM_ROUNDS; q++) {
+    for (uint32_t q = 0; q < CompactTile<RECLAIM_TILE>::ROUNDS; q++) {
         const uint32_t j = q * HONU_WAVES_PER_BLOCK + wv;
         const uint32_t t = j * HONU_WAVE + lane;
         if (t >= len) continue;
         const uint64_t r = (uint64_t)r0 + t;
-        const uint64_t kept_before = base + pre[j] + (uint32_t)__popcll(msk[j] & below);
-        if (!((msk[j] >> lane) & 1ull)) {
+        const uint64_t kept_before = K.kept_before(j, lane);
+        if (!K.kept_bit(j, lane)) {
             remap[r] = HONU_SEEK_NONE;
-            const uint64_t slot = kept + (r - kept_before);  // in [kept, nrec) with the count's masks
-            if (slot < nrec) len_out[slot] = 0;
+            const uint64_t slot = compact_removed_dst(kept, r, kept_before);  // in [kept, nrec) with the count's masks
+            if (compact_inside(slot, nrec)) len_out[slot] = 0;
             continue;
         }
-        if (kept_before >= kept) {  // (a mask or a count that is not the count's: inside the rows all the same)
+        if (!compact_inside(kept_before, kept)) {  // (masks or a count that are not the count's)
             remap[r] = HONU_SEEK_NONE;
             continue;
         }
@@ -209,7 +165,7 @@ hipError_t launch_key_reclaim(const LaunchGeom &g, const uint32_t *order, const 
         return hipSuccess;
     }
     const ReclaimWork W = reclaim_carve(work, nrec);
-    const uint64_t tiles = reclaim_tiles(nrec);
+    const uint64_t tiles = compact_tiles<RECLAIM_TILE>(nrec);
     if (!remap) remap = W.remap;
     if ((e = hipMemsetAsync(W.marks, 0, nrec, s)) != hipSuccess) return e;
     if (n)
@@ -217,7 +173,7 @@ hipError_t launch_key_reclaim(const LaunchGeom &g, const uint32_t *order, const 
                            (uint32_t)nrec, W.marks);
     hipLaunchKernelGGL(k_reclaim_count, dim3((unsigned)tiles), dim3(HONU_BLOCK), 0, s, (uint32_t)nrec, W);
     // (tiles <= nrec + 1 <= the state's rows: the caller)
-    if ((e = launch_scan(W.kept, tiles, 1, W.kept, kept, S, s)) != hipSuccess) return e;
+    if ((e = launch_scan(W.c.kept, tiles, 1, W.c.kept, kept, S, s)) != hipSuccess) return e;
     const ReclaimArrays A{keys, key_status, info, keys_out, key_status_out, info_out};
     hipLaunchKernelGGL(k_reclaim_place, dim3((unsigned)tiles), dim3(HONU_BLOCK), 0, s, rec_off, (uint32_t)nrec,
                        rec_bytes, A, kept, remap, source, rec_off_out, status, W);

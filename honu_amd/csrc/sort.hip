@@ -21,7 +21,7 @@
 // exclusive scan of the table (launch_scan, or one workgroup when the table
 // has more rows than the context's scan state is sized for), then a stable
 // scatter. No spin-wait of its own.
-#include "kernels.h"
+#include "compact.h"  // compact_lanes_below
 #include "keycol.h"
 
 namespace honu {
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(HONU_BLOCK) void k_sort_scatter(int d, uint64_t n, 
     const uint32_t *sword = reinterpret_cast<const uint32_t *>(skey) + digit_word(d);
     const uint32_t sh = digit_shift(d);
     const uint64_t base = (uint64_t)blockIdx.x * SORT_TILE + (uint64_t)wv * SORT_WAVE_KEYS + lane;
-    const uint64_t below = lane ? (~0ull >> (64 - lane)) : 0;
+    const uint64_t below = compact_lanes_below(lane);
     uint32_t dg[SORT_ITEMS], rank[SORT_ITEMS];
 #pragma unroll
     for (int it = 0; it < SORT_ITEMS; it++) {
