@@ -22,6 +22,7 @@
 //	pid.Next, Tombstone       lamport/pid.go:10-15, metadata/collection.go:56-63 -> (*Codec).NextVersions
 //	lamport.Compare, two replicas  lamport/scalar.go:15-78, keys/keys.go:35-36 -> (*Codec).CompareKeys
 //	Drop "to free up space"   store.go:314-322, 399-404 -> (*Codec).ReclaimRecords
+//	tx.Bucket(collectionID)   store.go:236-240, tx.go:112-120 -> (*Codec).RouteKeys
 package object
 
 /*
@@ -1428,6 +1429,73 @@ func (c *Codec) ReclaimRecords(o *KeyOrder, rec, recOff devBuf, nrec, recBytes u
 		}
 	}
 	out.Source = append([]uint32(nil), unsafe.Slice((*uint32)(hSource.p), out.Kept)...)
+	return out, nil
+}
+
+// Routed is what RouteKeys leaves on the device, and the one thing it reads
+// back: the offsets. Class c < k is row c of the table of collections, k the
+// records of no known collection (the nil bucket of tx.go:117-120), k + 1 the
+// positions that do not take part. Rows is a honu_list_row list (range = the
+// class), Local the row's index inside its class, Keys the 29-byte keys by
+// output row, Bucket the table row per record.
+type Routed struct {
+	Off   []uint64 // k + 3: the first output row of each class, then m
+	Count devBuf   // k + 2 counts on the device: Count + c is MergeKeys' valid count of collection c's segment
+
+	off                        devBuf // Off on the device: off + k is FetchObjects' total of the known collections' rows
+	Bucket, Rows, Local, Keys devBuf
+}
+
+func (r *Routed) Free() {
+	for _, d := range []devBuf{r.Count, r.off, r.Bucket, r.Rows, r.Local, r.Keys} {
+		if d.p != nil {
+			d.free()
+		}
+	}
+}
+
+// RouteKeys takes a batch apart by collection: the reference store has one
+// bbolt bucket per collection, named by the 16-byte collection ID
+// (tx.CreateBucketIfNotExists(info.ID[:]), store.go:236-240;
+// t.tx.Bucket(collectionID[:]), tx.go:112-120; Tx.Has and Tx.Exists,
+// tx.go:141-158), and every object carries its collection (collection.go:86).
+// ids holds record i's ID at idStride*i (the decoded rows with their address
+// + 112 and stride 352; a packed column with stride 16), status (or the zero
+// devBuf) leaves out the records that are not OK, seq (or the zero devBuf) is
+// the sequence to keep, SortKeys' order of the batch's keys, so that every
+// collection's rows come out in key order; table is the store's k collection
+// IDs, ascending and distinct; keys (or the zero devBuf) is gathered by output
+// row. The read of Off is the one host round trip a caller needs before the
+// per-collection MergeKeys, whose nb and segment pointers are host arguments.
+//
+// UNCOMPILED, like the rest of this file. honu_key_route is exercised on the
+// GPU from Python (tests/test_gpu_key_route.py, tests/test_gpu_store_collections.py),
+// graph capture included.
+func (c *Codec) RouteKeys(ids devBuf, idStride, m uint64, status, seq, table devBuf, k uint64, keys devBuf) (out *Routed, err error) {
+	out = &Routed{}
+	out.off, out.Count = device(uintptr(8*(k+3))), device(uintptr(8*(k+2)))
+	out.Bucket, out.Rows, out.Local = device(uintptr(4*m)), device(uintptr(uint64(C.honu_sizeof_list_row())*m)), device(uintptr(4*m))
+	if keys.p != nil {
+		out.Keys = device(uintptr(C.HONU_KEY_LEN * m))
+	}
+	workBytes := uint64(C.honu_key_route_workspace(C.uint64_t(m)))
+	work, hOff := device(uintptr(workBytes)), pinned(uintptr(8*(k+3)))
+	defer work.free()
+	defer hOff.free()
+	for _, s := range []C.int32_t{
+		C.honu_key_route(c.ctx, (*C.uint8_t)(ids.p), C.uint64_t(idStride), (*C.int32_t)(status.p), C.uint64_t(m),
+			(*C.uint32_t)(seq.p), (*C.uint8_t)(table.p), C.uint64_t(k), (*C.uint8_t)(keys.p),
+			(*C.uint32_t)(out.Bucket.p), (*C.honu_list_row)(out.Rows.p), (*C.uint32_t)(out.Local.p), (*C.uint8_t)(out.Keys.p),
+			(*C.uint64_t)(out.off.p), (*C.uint64_t)(out.Count.p), work.p, C.uint64_t(workBytes), c.stream),
+		C.honu_memcpy_d2h(hOff.p, out.off.p, C.uint64_t(8*(k+3)), c.stream),
+		C.honu_stream_sync(c.stream),
+	} {
+		if err = call("honu_key_route", s); err != nil {
+			out.Free()
+			return nil, err
+		}
+	}
+	out.Off = append([]uint64(nil), unsafe.Slice((*uint64)(hOff.p), k+3)...)
 	return out, nil
 }
 

@@ -72,6 +72,8 @@ _PROTOS = {
     "honu_key_reclaim_workspace": (U64, [U64]),
     "honu_key_reclaim": (I32, [P, P, P, U64, P, P, P, P, P, U64, U64, C.c_uint32, P, P, P, P, P, P, P, P, P, U64, P, P,
                                P, U64, P]),
+    "honu_key_route_workspace": (U64, [U64]),
+    "honu_key_route": (I32, [P, P, U64, P, U64, P, P, U64, P, P, P, P, P, P, P, P, U64, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -386,6 +386,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "compare_tile")) *value = compare_tile();    // read only: objects per workgroup of the compare
     else if (!strcmp(name, "compare_stage")) *value = compare_stage();  // read only: peer rows a workgroup of the compare stages in LDS
     else if (!strcmp(name, "reclaim_tile")) *value = reclaim_tile();  // read only: records per workgroup of the reclaim
+    else if (!strcmp(name, "route_stage")) *value = route_stage();  // read only: table rows a workgroup of the route stages in LDS
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -1070,6 +1071,37 @@ int32_t honu_key_reclaim(honu_ctx *ctx, const uint32_t *d_order, const uint64_t 
                               nrec, rec_bytes, d_order_out, d_remap, d_source, d_keys_out, d_key_status_out,
                               d_info_out, d_rec_off_out, d_status, d_values, val_cap, d_kept, d_val_total, d_work,
                               ctx->scan, (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a batch taken apart by collection: one bucket per collection ID
+// (store.go:236-240; tx.go:112-120, 141-158; collection.go:86)
+// ---------------------------------------------------------------------------
+uint64_t honu_key_route_workspace(uint64_t m) { return route_workspace_bytes(m); }
+
+int32_t honu_key_route(honu_ctx *ctx, const uint8_t *d_ids, uint64_t id_stride, const int32_t *d_status, uint64_t m,
+                       const uint32_t *d_seq, const uint8_t *d_table, uint64_t k, const uint8_t *d_keys,
+                       uint32_t *d_bucket, honu_list_row *d_rows, uint32_t *d_local, uint8_t *d_keys_out,
+                       uint64_t *d_bucket_off, uint64_t *d_bucket_count, void *d_work, uint64_t work_bytes,
+                       void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    // the classes are sorted with the context's scan state, which covers max_records rows
+    if (m > 0xFFFFFFFFull || m > ctx->max_n || k > 0xFFFFFFFCull) return HONU_E_WORKSPACE;
+    if (!d_bucket_off || !d_bucket_count) return arg_fail("null d_bucket_off or d_bucket_count");
+    if (m && !d_ids) return arg_fail("null d_ids");
+    if (id_stride < 16) return arg_fail("id_stride below 16");
+    if (k && !d_table) return arg_fail("null d_table");
+    if (!d_keys != !d_keys_out) return arg_fail("d_keys and d_keys_out go together");
+    if (!aligned(d_status, 4) || !aligned(d_seq, 4) || !aligned(d_bucket, 4) || !aligned(d_local, 4) ||
+        !aligned(d_bucket_off, 8) || !aligned(d_bucket_count, 8) || !aligned(d_rows, 16))
+        return arg_fail("status, seq, bucket and local 4-byte / offsets and counts 8-byte / rows 16-byte aligned");
+    const int32_t st = work_args(route_workspace_bytes(m), d_work, work_bytes, "honu_key_route_workspace(m)");
+    if (st) return st;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_key_route(d_ids, id_stride, d_status, m, d_seq, d_table, k, d_keys, d_bucket, d_rows, d_local,
+                            d_keys_out, d_bucket_off, d_bucket_count, d_work, ctx->scan, ctx->max_n,
+                            (hipStream_t)stream));
     return HONU_OK;
 }
 

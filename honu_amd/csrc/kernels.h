@@ -376,6 +376,20 @@ hipError_t launch_reclaim_copy(const LaunchGeom &g, const uint32_t *source, uint
                                const uint64_t *rec_off, const uint64_t *val_off, uint8_t *values,
                                uint64_t val_cap, hipStream_t s);
 
+// route.hip: a batch taken apart by collection, the bucket of every write (store.go:236-240; tx.go:112-120, 141-158;
+// collection.go:86): per position its class in the table of collections (k rows of 16 bytes, ascending; route_find.h),
+// then the stable partition of the positions by class through launch_sort_keys over the packed classes, so m must not
+// exceed scan_rows, the rows the context's scan state covers (its max_records). m <= 2^32 - 1, k <= 2^32 - 4. The
+// workspace is the caller's (route_workspace_bytes(m)); status, seq, keys with keys_out, bucket, rows and local may be
+// null. route_stage(): the table rows a workgroup stages in LDS at most
+uint32_t route_stage();
+uint64_t route_workspace_bytes(uint64_t m);
+hipError_t launch_key_route(const uint8_t *ids, uint64_t id_stride, const int32_t *status, uint64_t m,
+                            const uint32_t *seq, const uint8_t *table, uint64_t k, const uint8_t *keys,
+                            uint32_t *bucket, honu_list_row *rows, uint32_t *local, uint8_t *keys_out,
+                            uint64_t *bucket_off, uint64_t *bucket_count, void *work, const ScanState &S,
+                            uint64_t scan_rows, hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -38,7 +38,11 @@ such lists; the batch form is Codec.compare_keys (honu_key_compare).
 reclaim() is the host statement of what a Drop is for, "to free up space in
 the database" (store.go:314-322, 399-404): the records that delete() and
 compact() took out of the list taken out of the records and renumbered; the
-batch form is Codec.reclaim_records (honu_key_reclaim).
+batch form is Codec.reclaim_records (honu_key_reclaim). route() is the host
+statement of the bucket a write goes to, one per collection ID
+(store.go:236-240, tx.go:112-120): a batch of records of many collections
+partitioned stably by the store's table of collections; the batch form is
+Codec.route_keys (honu_key_route).
 """
 from __future__ import annotations
 
@@ -518,6 +522,79 @@ def reclaim(order: Sequence[int], valid: int, values: Sequence[bytes], keys: Opt
 
     return (order_out, remap, source, [bytes(values[r]) for r in source], gather(keys), gather(statuses),
             gather(info))
+
+
+class Route(NamedTuple):
+    """What route() returns. Class c < k is row c of the table, k the records
+    of no known collection, k + 1 the positions that do not take part."""
+    buckets: List[Optional[int]]  # per record: its table row, SEEK_NONE for none, None for a record no position names
+    rows: List[tuple]             # per output row: (class, position, record or SEEK_NONE, flags)
+    local: List[int]              # per output row: its index inside its class
+    keys: Optional[List[bytes]]   # per output row: the record's key, 29 zero bytes for no record; None without keys
+    offsets: List[int]            # k + 3: the first output row of each class, then m
+    counts: List[int]             # k + 2
+
+
+def route(ids: Sequence[bytes], table: Sequence[bytes], statuses: Optional[Sequence[int]] = None,
+          seq: Optional[Sequence[int]] = None, keys: Optional[Sequence[bytes]] = None) -> Route:
+    """A batch taken apart by collection. The store has one bbolt bucket per
+    collection, named by the 16-byte collection ID:
+    tx.CreateBucketIfNotExists(info.ID[:]) (store.go:236-240),
+    t.tx.Bucket(collectionID[:]) with a nil bucket ErrRepairCollection
+    (tx.go:112-120), Tx.Has and Tx.Exists (tx.go:141-158); every object
+    carries its collection (meta.CollectionID = c.ID, collection.go:86).
+
+    `ids` are the m records' collection IDs, `table` the store's k bucket
+    names, ascending by bytes.Compare and distinct. Position p < m stands for
+    record i = seq[p], or i = p without `seq`. Its class c is
+      the row of `table` that equals ids[i], when record i takes part
+            (`statuses` is None or statuses[i] == 0): the first such row;
+      k     when it takes part and no row does: the nil bucket;
+      k + 1 when it does not take part, or seq[p] names no record (not in
+            [0, m)).
+    Output row g is the g-th position when positions are ordered by (class,
+    p): a stable partition, Python's sorted(). With `seq` a key sort of the
+    batch (stable, the records that do not take part anywhere), every class's
+    rows stand in key order with equal keys in arrival order: what sort() of
+    that collection's keys alone gives, and so, as it stands, the B side of a
+    merge() into that collection's list.
+    Returns Route(buckets, rows, local, keys, offsets, counts): offsets[c] is
+    the first row of class c and offsets[k + 2] = m; counts[c] = offsets[c +
+    1] - offsets[c]; a row is (c, p, i or SEEK_NONE, LIST_ROW_HEAD on the
+    first row of every class that has rows, else 0); local[g] = g -
+    offsets[c]; keys[g] = bytes(keys[i]), or 29 zero bytes for a position
+    that names no record; buckets[i] = c for c < k, else SEEK_NONE, for every
+    record some position names. The batch form on the GPU is Codec.route_keys
+    (honu_key_route in include/honu_codec.h), which equals this."""
+    from .metadata import LIST_ROW_HEAD, SEEK_NONE
+    table = [bytes(t) for t in table]
+    m, k = len(ids), len(table)
+    buckets: List[Optional[int]] = [None] * m
+    classes = []
+    for p in range(m):
+        i = p if seq is None else int(seq[p])
+        if not 0 <= i < m:
+            classes.append((k + 1, p, SEEK_NONE))
+            continue
+        if statuses is not None and int(statuses[i]) != 0:
+            c = k + 1
+        else:
+            c = bisect.bisect_left(table, bytes(ids[i]))
+            if c == k or table[c] != bytes(ids[i]):
+                c = k
+        buckets[i] = c if c < k else SEEK_NONE
+        classes.append((c, p, i))
+    placed = sorted(classes, key=lambda row: row[0])  # stable: (class, p)
+    ascending = [row[0] for row in placed]
+    offsets = [bisect.bisect_left(ascending, c) for c in range(k + 3)]  # the rows of a class below c
+    counts = [offsets[c + 1] - offsets[c] for c in range(k + 2)]
+    rows, local, keys_out = [], [], None if keys is None else []
+    for g, (c, p, i) in enumerate(placed):
+        rows.append((c, p, i, LIST_ROW_HEAD if g == offsets[c] else 0))
+        local.append(g - offsets[c])
+        if keys is not None:
+            keys_out.append(bytes(KEY_SIZE) if i == SEEK_NONE else bytes(keys[i]))
+    return Route(buckets, rows, local, keys_out, offsets, counts)
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

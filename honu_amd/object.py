@@ -607,6 +607,58 @@ class Codec:
             key_status=i32(key_status_out, nrec) if key_status is not None else None,
             info=info_out[:32 * nrec] if info is not None else None)
 
+    def route_workspace(self, m: int):
+        """The workspace of route_keys for a batch of m positions (honu_key_route_workspace)."""
+        nbytes = int(self.lib.honu_key_route_workspace(m))
+        return self._empty(nbytes), nbytes
+
+    def route_keys(self, ids, m: int, table, k: int, id_stride: int = 16, status=None, seq=None, keys=None,
+                   want_bucket: bool = True, want_rows: bool = True, want_local: bool = True) -> "RouteResult":
+        """A batch taken apart by collection: one bbolt bucket per collection
+        ID (store.go:236-240; tx.go:112-120, 141-158; collection.go:86).
+        Record i's collection ID is the 16 bytes at `ids` + id_stride * i (a
+        uint8 tensor, or a device address: codec's decoded rows with
+        `dec.meta.data_ptr() + 112` and stride 352); `table` is the store's k
+        collection IDs, 16-byte rows, ascending and distinct; `status` (int32
+        per record) leaves out the records that are not OK; `seq` (sort_keys'
+        order of the batch's keys) is the sequence the partition keeps, so
+        that every bucket's rows come out in key order; `keys` (29 bytes per
+        record) are gathered by output row. keys.route is the host statement.
+        Returns a RouteResult of device tensors; nothing is read on the host.
+        The caller reads bucket_off once, for the nb and the segments of its
+        merge_keys calls; bucket_off[k:] is fetch_objects' `total` as it
+        stands."""
+        bucket = self._empty(4 * m) if want_bucket else None
+        rows = self._empty(16 * m) if want_rows else None
+        local = self._empty(4 * m) if want_local else None
+        keys_out = self._empty(29 * m) if keys is not None else None
+        off, count = self._empty(8 * (k + 3)), self._empty(8 * (k + 2))
+        work, work_bytes = self.route_workspace(m)
+        _lib.check(self.lib.honu_key_route(
+            self.ctx, _lib.ptr(ids), id_stride, _lib.ptr(status), m, _lib.ptr(seq), _lib.ptr(table), k, _lib.ptr(keys),
+            _lib.ptr(bucket), _lib.ptr(rows), _lib.ptr(local), _lib.ptr(keys_out), _lib.ptr(off), _lib.ptr(count),
+            _lib.ptr(work), work_bytes, self.stream), "honu_key_route")
+        torch = _torch()
+        i32 = lambda t: t[:4 * m].view(torch.int32)  # noqa: E731
+        return RouteResult(
+            bucket=i32(bucket) if want_bucket else None,
+            rows=rows[:16 * m].view(torch.int32).view(m, 4) if want_rows else None,
+            local=i32(local) if want_local else None, keys=keys_out[:29 * m] if keys is not None else None,
+            bucket_off=off[:8 * (k + 3)].view(torch.int64), bucket_count=count[:8 * (k + 2)].view(torch.int64))
+
+
+@dataclass
+class RouteResult:
+    """What Codec.route_keys returns, all on the device. Class c < k is row c
+    of the table, k the records of no known collection, k + 1 the positions
+    that do not take part."""
+    bucket: object        # int32[m] or None: per record its table row, SEEK_NONE (-1) for none
+    rows: object          # int32[m, 4] or None: honu_list_row (range = class, pos, record, flags), by output row
+    local: object         # int32[m] or None: the output row's index inside its class
+    keys: object          # uint8[29 m] or None: the keys by output row
+    bucket_off: object    # int64[k + 3]: the first output row of each class, then m
+    bucket_count: object  # int64[k + 2]
+
 
 @dataclass
 class ReclaimResult:

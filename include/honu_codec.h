@@ -27,6 +27,7 @@
  *   pid.Next, Tombstone (batch) lamport/pid.go:10-15, collection.go:75-137  honu_key_next (the version each write writes)
  *   lamport.Compare (two columns) lamport/scalar.go:15-78, keys/keys.go:35-36  honu_key_compare (who is later, what to send, forks)
  *   Drop "to free up space"     store.go:314-322, 399-404  honu_key_reclaim (the records arena compacted to the records the column names)
+ *   tx.Bucket(collectionID[:])  store.go:236-240, tx.go:112-120, 141-158  honu_key_route (a mixed batch partitioned by its collections' buckets)
  *   lani.Encodable.Size()       lani/lani.go:9-12     (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -1349,6 +1350,110 @@ int32_t honu_key_reclaim(honu_ctx *ctx, const uint32_t *d_order, const uint64_t 
                          uint64_t *d_rec_off_out, int32_t *d_status /* optional */,
                          uint8_t *d_values, uint64_t val_cap, uint64_t *d_kept, uint64_t *d_val_total,
                          void *d_work, uint64_t work_bytes, void *stream);
+
+/* Bytes of honu_key_route's workspace for a batch of m positions: the packed
+ * classes, their sorted column, the order and honu_sort_keys' own workspace. A
+ * multiple of 256, monotonic in m, 0 for m == 0; needs no device. */
+uint64_t honu_key_route_workspace(uint64_t m);
+
+/* A batch taken apart by collection. Every call above works on one sorted
+ * 29-byte column, one bbolt bucket. The reference store has one bucket per
+ * collection, named by the 16-byte collection ID:
+ * tx.CreateBucketIfNotExists(info.ID[:]) (store.go:236-240);
+ * t.tx.Bucket(collectionID[:]), where a nil bucket is ErrRepairCollection
+ * (tx.go:112-120); Tx.Has(collection, id) and Tx.Exists(collection, id)
+ * (tx.go:141-158). Every object carries the collection it belongs to
+ * (meta.CollectionID = c.ID, collection.go:86; honu_meta.collection_id, offset
+ * 112). A marshalled batch, a write-feed slot or the batch that
+ * honu_key_compare -> honu_key_list -> honu_key_fetch ships to a peer holds
+ * records of many collections mixed together; this call looks every record's
+ * collection ID up in the store's table of collections and partitions the
+ * batch stably by the bucket found. honu_amd/keys.py route() is the host
+ * statement; this call equals it.
+ * Inputs. Record i's collection ID is the 16 bytes at d_ids + id_stride * i,
+ * i < m; d_ids may have any byte alignment, id_stride >= 16. (const uint8_t
+ * *)d_meta + 112 with stride 352 makes the decoded rows the input as they
+ * stand; stride 16 takes a packed ID column, for example the collection
+ * column of a batch of Tx.Has(collection, id) probes. d_status (optional, m
+ * values): record i takes part when d_status is NULL or d_status[i] ==
+ * HONU_OK. d_table is the store's collections: k rows of 16 bytes at any byte
+ * alignment, ascending by bytes.Compare and distinct, the sorted list of
+ * bucket names. d_keys (optional, 29 m bytes, any byte alignment) is the
+ * batch's key column, by record.
+ * Sequence. Position p < m stands for record i = d_seq[p], or i = p without
+ * d_seq. With d_seq the order honu_sort_keys wrote for this batch's keys and
+ * d_status the status column that sort was given, each bucket's rows come out
+ * in key order, equal keys in arrival order: a stable partition of a sorted
+ * sequence leaves every part sorted, which is exactly what honu_sort_keys
+ * would have returned for that collection's records alone. One sort and one
+ * route replace k sorts, and each segment is, as it stands, the B side of a
+ * honu_key_merge into that collection's column.
+ * Classes. Each position gets a class c: c < k when the record takes part
+ * and row c of d_table equals its ID (on garbage, the first such row the
+ * search meets); c = k when it takes part and no row equals its ID, the nil
+ * bucket of tx.go:117-120; c = k + 1 when the record does not take part
+ * (status not HONU_OK) or d_seq[p] >= m, which names no record.
+ * Outputs. Output row g is the g-th position when the positions are ordered
+ * by (class, p): a stable partition. d_bucket_off[c], c in [0, k + 2], is the
+ * first row of class c, d_bucket_off[k + 2] = m, and d_bucket_count[c] =
+ * d_bucket_off[c + 1] - d_bucket_off[c], c in [0, k + 1]. d_bucket_off + k is
+ * therefore a valid d_total for honu_key_fetch (the routed rows), and
+ * d_bucket_count + c a valid d_valid_b for honu_key_merge.
+ * d_rows[g] (optional) = {range: c, pos: p, record: i, flags}: record is
+ * HONU_SEEK_NONE when d_seq[p] >= m; flags carries HONU_LIST_ROW_HEAD on the
+ * first row of every non-empty class, the two tail classes included, and no
+ * other bit. The rows are a honu_list_row list: honu_key_fetch gathers the
+ * records bucket by bucket with nothing read on the host.
+ * d_local[g] (optional) = g - d_bucket_off[c]: the record's index inside its
+ * collection's segment once gathered, that is, honu_key_merge's d_order_b.
+ * d_keys_out + 29 g (optional) is the 29 bytes of d_keys row i, moved as
+ * bytes and never a byte past them, 29 zero bytes when the position names no
+ * record; it is given together with d_keys and not without it.
+ * d_bucket[i] (optional) = c for c < k, else HONU_SEEK_NONE, written for
+ * every i some position names: every record when d_seq is a permutation or
+ * absent. It answers a batch of Tx.Has / Tx.Exists probes' bucket lookups.
+ * The write set is exactly d_bucket_off[0, k + 3), d_bucket_count[0, k + 2),
+ * d_rows[0, m), d_local[0, m), d_keys_out[0, 29 m) and the named d_bucket
+ * entries, besides the workspace. With m == 0 only the offsets and counts are
+ * written, all zero.
+ * Garbage in. A table out of order or with repeats, or a d_seq that is no
+ * permutation, may give wrong classes or rows. It never gives an access
+ * outside the arrays or a search that does not end: a table row asked lies
+ * in [0, k), a record read is below m, and every bisection's bracket shrinks
+ * at each step.
+ * What follows the call. honu_key_merge's nb and the segments' pointers are
+ * host arguments, so one host read of d_bucket_off follows a route, as one
+ * read of d_kept follows a reclaim and a caller reads a batch's byte total to
+ * size its arena.
+ * d_work is honu_key_route_workspace(m) bytes, 256-byte aligned (unused, and
+ * NULL allowed, when that is 0). Three steps on `stream`: the classes, a
+ * honu_sort_keys over them with the context's scan state (whose state covers
+ * max_records rows, hence m <= honu_ctx_max_records, and one context serves
+ * one stream at a time), the rows and offsets. Asynchronous on `stream`, no
+ * host synchronisation, no allocation; the grids are sized from m and k;
+ * replays from a captured graph, also after the IDs, the statuses and the
+ * table's bytes were changed on the device between replays.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for m above
+ * honu_ctx_max_records or 2^32 - 1, or k above 2^32 - 4; HONU_E_ARG for a
+ * NULL ctx, d_bucket_off or d_bucket_count, a NULL d_ids with m > 0,
+ * id_stride below 16, a NULL d_table with k > 0, exactly one of d_keys and
+ * d_keys_out, work_bytes below honu_key_route_workspace(m), a NULL or
+ * misaligned (256) workspace with m > 0, or a misaligned pointer (4 bytes:
+ * d_status, d_seq, d_bucket, d_local; 8 bytes: the offsets and counts; 16
+ * bytes: d_rows).
+ * The get-only param "route_stage" is the table rows a workgroup stages in
+ * LDS at most; a longer table is searched in global memory, with the same
+ * classes. */
+int32_t honu_key_route(honu_ctx *ctx, const uint8_t *d_ids, uint64_t id_stride,
+                       const int32_t *d_status /* optional */, uint64_t m,
+                       const uint32_t *d_seq /* optional */,
+                       const uint8_t *d_table, uint64_t k,
+                       const uint8_t *d_keys /* optional */,
+                       uint32_t *d_bucket /* optional */,
+                       honu_list_row *d_rows /* optional */, uint32_t *d_local /* optional */,
+                       uint8_t *d_keys_out /* with d_keys */,
+                       uint64_t *d_bucket_off, uint64_t *d_bucket_count,
+                       void *d_work, uint64_t work_bytes, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
