@@ -1499,6 +1499,56 @@ func (c *Codec) RouteKeys(ids devBuf, idStride, m uint64, status, seq, table dev
 	return out, nil
 }
 
+// Buckets is a bucketed column on the device: k buckets' sorted 29-byte rows
+// end to end in one arena of N rows, one uint32 record index per row, k + 1
+// uint64 offsets and (optionally) k uint64 counts of valid rows. Bucket c is
+// the bucket of row c of the store's sorted table of collections.
+type Buckets struct {
+	K, N                      uint64 // N: the rows the arena holds, a host bound
+	Sorted, Order, Off, Count devBuf
+}
+
+func (b *Buckets) Free() {
+	for _, d := range []devBuf{b.Sorted, b.Order, b.Off, b.Count} {
+		if d.p != nil {
+			d.free()
+		}
+	}
+}
+
+// MergeBuckets is collections.Put (store.go:232, 395, 530) for a whole routed
+// batch, every record into the bucket tx.Bucket(collectionID[:]) names
+// (store.go:236-240, tx.go:112-120): per bucket the stable merge of a's valid
+// rows and the rows RouteKeys left for that collection, a's first on equal
+// keys, the buckets tight behind each other in a new arena of a.N + m rows. r
+// is passed as it stands (Keys the rows, Local the order, its device offsets,
+// m the routed batch's positions); base (k uint32 on the device, or the zero
+// devBuf with bBase) is added to b's record indices per bucket. Nothing is read
+// on the host: the caller that has gone through RouteKeys has paid its read of
+// Off already, one that calls honu_key_route itself pays none.
+//
+// UNCOMPILED, like the rest of this file. honu_key_merge_buckets is exercised
+// on the GPU from Python (tests/test_gpu_key_merge_buckets.py,
+// tests/test_gpu_store_buckets.py), graph capture included.
+func (c *Codec) MergeBuckets(a *Buckets, r *Routed, m uint64, base devBuf, bBase uint32) (*Buckets, error) {
+	n := a.N + m
+	if n > 0xFFFFFFFF {
+		return nil, fmt.Errorf("%d rows: an order indexes at most 2^32 - 1", n)
+	}
+	o := &Buckets{K: a.K, N: n}
+	o.Sorted, o.Order = device(uintptr(C.HONU_KEY_LEN*n)), device(uintptr(4*n))
+	o.Off, o.Count = device(uintptr(8*(a.K+1))), device(uintptr(8*a.K))
+	s := C.honu_key_merge_buckets(c.ctx, C.uint64_t(a.K), (*C.uint8_t)(a.Sorted.p), (*C.uint32_t)(a.Order.p),
+		(*C.uint64_t)(a.Off.p), (*C.uint64_t)(a.Count.p), C.uint64_t(a.N), (*C.uint8_t)(r.Keys.p),
+		(*C.uint32_t)(r.Local.p), (*C.uint64_t)(r.off.p), C.uint64_t(m), (*C.uint32_t)(base.p), C.uint32_t(bBase),
+		(*C.uint8_t)(o.Sorted.p), (*C.uint32_t)(o.Order.p), (*C.uint64_t)(o.Off.p), (*C.uint64_t)(o.Count.p), c.stream)
+	if err := call("honu_key_merge_buckets", s); err != nil {
+		o.Free()
+		return nil, err
+	}
+	return o, nil
+}
+
 // Has is Collection.Has (collection.go:47-51) for a batch: key != nil &&
 // bytes.HasPrefix(key, probe) of the key Seek lands on.
 func (c *Codec) Has(o *KeyOrder, probes [][]byte) ([]bool, error) {

@@ -74,6 +74,7 @@ _PROTOS = {
                                P, U64, P]),
     "honu_key_route_workspace": (U64, [U64]),
     "honu_key_route": (I32, [P, P, U64, P, U64, P, P, U64, P, P, P, P, P, P, P, P, U64, P]),
+    "honu_key_merge_buckets": (I32, [P, U64, P, P, P, P, U64, P, P, P, U64, P, C.c_uint32, P, P, P, P, P]),
     "honu_decode_headers": (I32, [P, P, P, U64, P, P]),
     "honu_decode_data": (I32, [P, P, P, U64, P, P, U64, P, P]),
     "honu_decode_data_place": (I32, [P, P, P, U64, P, U64, P, P]),

@@ -387,6 +387,7 @@ int32_t honu_ctx_get_param(const honu_ctx *ctx, const char *name, int64_t *value
     else if (!strcmp(name, "compare_stage")) *value = compare_stage();  // read only: peer rows a workgroup of the compare stages in LDS
     else if (!strcmp(name, "reclaim_tile")) *value = reclaim_tile();  // read only: records per workgroup of the reclaim
     else if (!strcmp(name, "route_stage")) *value = route_stage();  // read only: table rows a workgroup of the route stages in LDS
+    else if (!strcmp(name, "merge_buckets_stage")) *value = merge_buckets_stage();  // read only: buckets of a tile whose offsets the bucketed merge stages in LDS
     else return arg_fail(name);
     return HONU_OK;
 }
@@ -1102,6 +1103,35 @@ int32_t honu_key_route(honu_ctx *ctx, const uint8_t *d_ids, uint64_t id_stride, 
     HIPCHK(launch_key_route(d_ids, id_stride, d_status, m, d_seq, d_table, k, d_keys, d_bucket, d_rows, d_local,
                             d_keys_out, d_bucket_off, d_bucket_count, d_work, ctx->scan, ctx->max_n,
                             (hipStream_t)stream));
+    return HONU_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a routed batch of Puts into every collection's bucket at once
+// (store.go:232-240, 395, 530; tx.go:112-120)
+// ---------------------------------------------------------------------------
+int32_t honu_key_merge_buckets(honu_ctx *ctx, uint64_t k, const uint8_t *d_sorted_a, const uint32_t *d_order_a,
+                               const uint64_t *d_off_a, const uint64_t *d_count_a, uint64_t na,
+                               const uint8_t *d_sorted_b, const uint32_t *d_order_b, const uint64_t *d_off_b,
+                               uint64_t nb, const uint32_t *d_base, uint32_t b_base, uint8_t *d_sorted_out,
+                               uint32_t *d_order_out, uint64_t *d_off_out, uint64_t *d_count_out, void *stream) {
+    if (!ctx) return arg_fail("ctx");
+    if (na > 0xFFFFFFFFull || nb > 0xFFFFFFFFull || na + nb > 0xFFFFFFFFull || k > 0xFFFFFFFCull)
+        return HONU_E_WORKSPACE;
+    // with counts the buckets' rows are scanned with the context's scan state, which covers max_records rows
+    if (d_count_a && k + 1 > ctx->max_n) return HONU_E_WORKSPACE;
+    if (!d_off_a || !d_off_b || !d_off_out) return arg_fail("null offsets");
+    if ((na && !d_sorted_a) || (nb && !d_sorted_b) || (na + nb && !d_sorted_out)) return arg_fail("null column");
+    if (d_order_out && na && !d_order_a) return arg_fail("d_order_out needs d_order_a");
+    if (!d_base && (uint64_t)b_base + nb > 0xFFFFFFFFull) return arg_fail("b_base + nb above 2^32 - 1");
+    if (!aligned(d_order_a, 4) || !aligned(d_order_b, 4) || !aligned(d_order_out, 4) || !aligned(d_base, 4) ||
+        !aligned(d_off_a, 8) || !aligned(d_count_a, 8) || !aligned(d_off_b, 8) || !aligned(d_off_out, 8) ||
+        !aligned(d_count_out, 8))
+        return arg_fail("orders and bases 4-byte / offsets and counts 8-byte aligned");
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(launch_merge_buckets(k, d_sorted_a, d_order_a, d_off_a, d_count_a, na, d_sorted_b, d_order_b, d_off_b, nb,
+                                d_base, b_base, d_sorted_out, d_order_out, d_off_out, d_count_out, ctx->scan,
+                                (hipStream_t)stream));
     return HONU_OK;
 }
 

@@ -390,6 +390,19 @@ hipError_t launch_key_route(const uint8_t *ids, uint64_t id_stride, const int32_
                             uint64_t *bucket_off, uint64_t *bucket_count, void *work, const ScanState &S,
                             uint64_t scan_rows, hipStream_t s);
 
+// merge_buckets.hip: a routed batch merged into every bucket's column at once (store.go:232-240, 395, 530; tx.go:112-120):
+// two bucketed columns (k buckets end to end in one arena, offsets k + 1 values; bucket_off.h), per bucket the stable
+// merge of its valid A rows and its B rows, the buckets tight behind each other. na + nb <= 2^32 - 1, k <= 2^32 - 4; oa,
+// count_a, ob, base, order and count_out may be null. With count_a the buckets' rows go through launch_scan in off_out
+// (k values, the total to off_out[k]): k must not exceed the rows the context's scan state covers (its max_records).
+// merge_buckets_stage(): the buckets a tile touches at most for its slice of offsets to be staged in LDS
+uint32_t merge_buckets_stage();
+hipError_t launch_merge_buckets(uint64_t k, const uint8_t *sa, const uint32_t *oa, const uint64_t *off_a,
+                                const uint64_t *count_a, uint64_t na, const uint8_t *sb, const uint32_t *ob,
+                                const uint64_t *off_b, uint64_t nb, const uint32_t *base, uint32_t b_base, uint8_t *out,
+                                uint32_t *order, uint64_t *off_out, uint64_t *count_out, const ScanState &S,
+                                hipStream_t s);
+
 hipError_t launch_hbm_probe(int mode, const void *src, void *dst, uint64_t bytes, uint32_t blocks,
                             uint32_t *sink, hipStream_t s);
 hipError_t launch_gen_payload(const LaunchGeom &g, uint64_t seed, uint64_t first, uint64_t n,

@@ -42,7 +42,10 @@ batch form is Codec.reclaim_records (honu_key_reclaim). route() is the host
 statement of the bucket a write goes to, one per collection ID
 (store.go:236-240, tx.go:112-120): a batch of records of many collections
 partitioned stably by the store's table of collections; the batch form is
-Codec.route_keys (honu_key_route).
+Codec.route_keys (honu_key_route). merge_buckets() is the host statement of
+the write that follows, collections.Put (store.go:232, 395, 530) of the whole
+routed batch, every record into its collection's bucket: merge() bucket by
+bucket; the batch form is Codec.merge_bucket_keys (honu_key_merge_buckets).
 """
 from __future__ import annotations
 
@@ -595,6 +598,38 @@ def route(ids: Sequence[bytes], table: Sequence[bytes], statuses: Optional[Seque
         if keys is not None:
             keys_out.append(bytes(KEY_SIZE) if i == SEEK_NONE else bytes(keys[i]))
     return Route(buckets, rows, local, keys_out, offsets, counts)
+
+
+class BucketRow(NamedTuple):
+    key: bytes
+    side: int   # 0: the row came from a, 1: from b
+    index: int  # its index inside that side's bucket
+
+
+def merge_buckets(a: Sequence[Sequence[bytes]], b: Sequence[Sequence[bytes]],
+                  counts: Optional[Sequence[int]] = None) -> List[List[BucketRow]]:
+    """A routed batch of Puts into every collection's bucket at once
+    (collections.Put, store.go:232, 395, 530, into the bucket
+    tx.Bucket(collectionID[:]) names, store.go:236-240, tx.go:112-120): `a`
+    and `b` are k buckets each, bucket c a sorted list of keys, a's the
+    resident rows and b's what route() left for row c of the table;
+    `counts[c]`, when given, says how many of a[c]'s rows are valid, its first
+    min(counts[c], len(a[c])). Bucket c of the result is merge() of a[c]'s
+    valid rows and b[c]: on equal keys a's rows before b's, each side in its
+    own order; invalid rows are dropped, so the result is tight. Every row is
+    (key, side, index): where it came from. Concatenated, the buckets are the
+    rows Codec.merge_bucket_keys (honu_key_merge_buckets in
+    include/honu_codec.h) writes, and the lengths its counts."""
+    if len(a) != len(b) or (counts is not None and len(counts) != len(a)):
+        raise ValueError("a, b and counts have one entry per bucket")
+    out = []
+    for c in range(len(a)):
+        va = len(a[c]) if counts is None else min(int(counts[c]), len(a[c]))
+        # (key, side, index) orders as the key, then a before b: merge()'s own tie rule
+        rows = merge([(bytes(key), 0, i) for i, key in enumerate(a[c][:va])],
+                     [(bytes(key), 1, i) for i, key in enumerate(b[c])])
+        out.append([BucketRow(*row) for row in rows])
+    return out
 
 
 def has(sorted_keys: Sequence[bytes], probe: bytes) -> bool:

@@ -647,6 +647,50 @@ class Codec:
             bucket_off=off[:8 * (k + 3)].view(torch.int64), bucket_count=count[:8 * (k + 2)].view(torch.int64))
 
 
+    def merge_bucket_keys(self, k: int, sorted_a, order_a, off_a, sorted_b, order_b, off_b, count_a=None,
+                          nb: Optional[int] = None, base=None, b_base: int = 0,
+                          want_count: bool = True) -> "BucketsResult":
+        """A routed batch of Puts into every collection's bucket at once
+        (store.go:232-240, 395, 530; tx.go:112-120). A and B are bucketed
+        columns on the device: k buckets' sorted 29-byte rows end to end
+        (`sorted_a`, `sorted_b`), one int32 record index per row (`order_a`,
+        `order_b`, or None), and k + 1 int64 offsets (`off_a`, `off_b`);
+        `count_a` (int64[k], optional) gives a bucket's valid rows.
+        route_keys' outputs are B as they stand: keys, local (or None),
+        bucket_off, with `nb` = the route's m (default: sorted_b's rows). B's
+        row g of bucket c gets (order_b[g], or g) + (base[c], int32[k] on the
+        device, or the scalar b_base). keys.merge_buckets is the host
+        statement. Returns a BucketsResult of device tensors sized by na + nb;
+        nothing is read on the host: the rows behind off[k] are not written.
+        The order is None unless order_a is given (or A has no rows)."""
+        na = sorted_a.numel() // 29 if sorted_a is not None else 0
+        if nb is None:
+            nb = sorted_b.numel() // 29 if sorted_b is not None else 0
+        with_order = order_a is not None or na == 0
+        out = self._empty(29 * (na + nb))
+        order = self._empty(4 * (na + nb)) if with_order else None
+        off = self._empty(8 * (k + 1))
+        count = self._empty(8 * k) if want_count else None
+        _lib.check(self.lib.honu_key_merge_buckets(
+            self.ctx, k, _lib.ptr(sorted_a), _lib.ptr(order_a), _lib.ptr(off_a), _lib.ptr(count_a), na,
+            _lib.ptr(sorted_b), _lib.ptr(order_b), _lib.ptr(off_b), nb, _lib.ptr(base), b_base, _lib.ptr(out),
+            _lib.ptr(order), _lib.ptr(off), _lib.ptr(count), self.stream), "honu_key_merge_buckets")
+        torch = _torch()
+        return BucketsResult(
+            sorted=out[:29 * (na + nb)], order=order[:4 * (na + nb)].view(torch.int32) if with_order else None,
+            off=off[:8 * (k + 1)].view(torch.int64), count=count[:8 * k].view(torch.int64) if want_count else None)
+
+
+@dataclass
+class BucketsResult:
+    """What Codec.merge_bucket_keys returns, all on the device: a bucketed
+    column, bucket c the rows [off[c], off[c + 1])."""
+    sorted: object  # uint8[29 (na + nb)]: the first off[k] rows are written
+    order: object   # int32[na + nb] or None
+    off: object     # int64[k + 1]
+    count: object   # int64[k] or None: the rows of each bucket
+
+
 @dataclass
 class RouteResult:
     """What Codec.route_keys returns, all on the device. Class c < k is row c

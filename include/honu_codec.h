@@ -28,6 +28,7 @@
  *   lamport.Compare (two columns) lamport/scalar.go:15-78, keys/keys.go:35-36  honu_key_compare (who is later, what to send, forks)
  *   Drop "to free up space"     store.go:314-322, 399-404  honu_key_reclaim (the records arena compacted to the records the column names)
  *   tx.Bucket(collectionID[:])  store.go:236-240, tx.go:112-120, 141-158  honu_key_route (a mixed batch partitioned by its collections' buckets)
+ *   bucket.Put (every bucket)   store.go:232-240, 395, 530, tx.go:112-120  honu_key_merge_buckets (a routed batch merged into all buckets' columns)
  *   lani.Encodable.Size()       lani/lani.go:9-12     (host only; Size() is a Grow hint, not bytes)
  *
  * Conventions
@@ -1424,7 +1425,8 @@ uint64_t honu_key_route_workspace(uint64_t m);
  * What follows the call. honu_key_merge's nb and the segments' pointers are
  * host arguments, so one host read of d_bucket_off follows a route, as one
  * read of d_kept follows a reclaim and a caller reads a batch's byte total to
- * size its arena.
+ * size its arena. honu_key_merge_buckets (below) takes the offsets on the
+ * device and needs no such read.
  * d_work is honu_key_route_workspace(m) bytes, 256-byte aligned (unused, and
  * NULL allowed, when that is 0). Three steps on `stream`: the classes, a
  * honu_sort_keys over them with the context's scan state (whose state covers
@@ -1454,6 +1456,87 @@ int32_t honu_key_route(honu_ctx *ctx, const uint8_t *d_ids, uint64_t id_stride,
                        uint8_t *d_keys_out /* with d_keys */,
                        uint64_t *d_bucket_off, uint64_t *d_bucket_count,
                        void *d_work, uint64_t work_bytes, void *stream);
+
+/* A routed batch merged into every collection's bucket at once: collections.Put
+ * (store.go:232, 395, 530) for a whole mixed batch, each record into the bucket
+ * tx.Bucket(collectionID[:]) names (store.go:236-240, tx.go:112-120). What k
+ * calls of honu_key_merge do after one host read of honu_key_route's
+ * d_bucket_off, in one call with nothing read on the host.
+ * honu_amd/keys.py merge_buckets() is the host statement; this call equals it.
+ * The bucketed column. All k buckets' columns lie end to end in one arena:
+ * d_sorted holds 29-byte rows at any byte alignment, d_order one uint32 record
+ * index per row, d_off is uint64[k + 1], ascending, d_off[0] = 0. Bucket c is
+ * the rows [d_off[c], d_off[c + 1]), sorted by bytes.Compare; it is the bucket
+ * named by row c of the store's sorted table of collections (honu_key_route's
+ * d_table). An optional d_count (uint64[k]) gives a bucket's valid rows,
+ * min(d_count[c], d_off[c + 1] - d_off[c]), its first; without it every row
+ * of a bucket is valid. A view (d_sorted + 29 off[c], d_order + off[c],
+ * d_count + c, rows) is an input of every per-bucket call above, and a
+ * honu_key_delete over a view that writes its d_valid_out into a count array
+ * produces the next call's d_count_a. honu_key_route's outputs are a bucketed
+ * column as they stand: d_keys_out the rows, d_bucket_off the offsets (its
+ * first k + 1 entries are used; the two tail classes lie behind
+ * d_bucket_off[k] and reach no bucket), d_local the order.
+ * Inputs. A is the resident column (na rows in its arena, d_count_a
+ * optional), B the batch (nb rows in its arena: the route's m). na and nb are
+ * host bounds; everything else is read on the device. Every offset is clamped
+ * to its arena: ea[c] = min(d_off_a[c], na), eb[c] = min(d_off_b[c], nb).
+ * Bucket c takes A's first va[c] rows from ea[c], va[c] = min(d_count_a[c],
+ * ea[c + 1] - ea[c]) (the whole difference without d_count_a), and all vb[c] =
+ * eb[c + 1] - eb[c] rows of B from eb[c].
+ * Outputs. d_off_out[0] = 0, d_off_out[c + 1] = d_off_out[c] + va[c] + vb[c]
+ * and d_count_out[c] (optional) = va[c] + vb[c]. Output rows [d_off_out[c],
+ * d_off_out[c + 1]) are the stable merge of bucket c's valid A rows and its B
+ * rows by bytes.Compare: on equal keys every A row before every B row, each
+ * side in its own order, the first va[c] + vb[c] rows honu_key_merge writes
+ * for those two views. The output is tight: invalid rows of A are dropped, so
+ * the call also squeezes what per-bucket deletes left. An A row keeps its
+ * index; B's row g of bucket c gets (d_order_b ? d_order_b[g] : g) + (d_base ?
+ * d_base[c] : b_base), modulo 2^32. With d_order_b the route's d_local and
+ * d_base the buckets' record counts every bucket keeps its own record
+ * numbering, exactly k calls of honu_key_merge with b_base = d_base[c]; with
+ * both NULL and a scalar b_base the store has one numbering, routed row g
+ * being record b_base + g of what honu_key_fetch gathered. d_order_out NULL
+ * ignores every order; when given it needs d_order_a whenever na > 0.
+ * The write set is exactly d_sorted_out[0, 29 T), d_order_out[0, T) with T =
+ * d_off_out[k], d_off_out[0, k + 1) and d_count_out[0, k): nothing at or past
+ * row T. The outputs hold na + nb rows and must not overlap the inputs; the
+ * caller ping-pongs two arenas, as with honu_key_merge, and sizes them by na +
+ * nb, so no host read follows a route. k == 0 writes d_off_out[0] = 0 alone,
+ * na + nb == 0 the offsets and counts alone.
+ * Garbage in. Offsets that do not ascend, or d_off[0] != 0, may give wrong
+ * rows. They never give an access outside the arrays or a search that does
+ * not end: every row read lies below na or nb, every offset entry read in
+ * [0, k], every output row written below na + nb, and every bracket shrinks
+ * at each step.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; the grids
+ * are sized from na + nb and from k. Without d_count_a the offsets are the sum
+ * of two prefix arrays and the call is one launch with no state outside it.
+ * With d_count_a the buckets' rows are scanned with the context's scan state
+ * (whose state covers max_records rows, hence k + 1 <= honu_ctx_max_records,
+ * and one context serves one stream at a time). Replays from a captured graph,
+ * also after the offsets, counts and rows were changed on the device.
+ * Refusals, each storing nothing: HONU_E_WORKSPACE for na + nb above 2^32 - 1,
+ * k above 2^32 - 4, or with d_count_a k + 1 above honu_ctx_max_records;
+ * HONU_E_ARG for a NULL ctx, d_off_a, d_off_b or d_off_out, a NULL column with
+ * a row count other than 0 (d_sorted_a with na, d_sorted_b with nb,
+ * d_sorted_out with na + nb), d_order_out without d_order_a when na > 0,
+ * b_base + nb above 2^32 - 1 when d_base is NULL, or a misaligned pointer (4
+ * bytes: the orders and d_base; 8 bytes: the offsets and counts).
+ * The get-only param "merge_buckets_stage" is the buckets an output tile of
+ * "merge_tile" rows touches at most for its slice of offsets to be staged in
+ * LDS; above that the slice is searched in global memory, with the same
+ * rows. */
+int32_t honu_key_merge_buckets(honu_ctx *ctx, uint64_t k,
+                               const uint8_t *d_sorted_a, const uint32_t *d_order_a /* optional */,
+                               const uint64_t *d_off_a /* k + 1 */,
+                               const uint64_t *d_count_a /* optional, k */, uint64_t na,
+                               const uint8_t *d_sorted_b, const uint32_t *d_order_b /* optional */,
+                               const uint64_t *d_off_b /* k + 1 */, uint64_t nb,
+                               const uint32_t *d_base /* optional, k */, uint32_t b_base,
+                               uint8_t *d_sorted_out, uint32_t *d_order_out /* optional */,
+                               uint64_t *d_off_out /* k + 1 */,
+                               uint64_t *d_count_out /* optional, k */, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* System objects (object/system.go): metadata.Collection with its Indexes.  */
