@@ -633,6 +633,10 @@ typedef struct honu_seek {
  * sort's) enables first and latest, which are its values at pos and end - 1.
  * d_info (n rows; needs d_order) enables the two LIVE bits; an index of
  * d_order that is not below n reads row n - 1 there, as in honu_key_objects.
+ * d_info is indexed by record and clamped by n, the column's rows: the LIVE
+ * bits answer for the column only while every index in its valid rows is below
+ * n. Over a view of a bucketed column (honu_key_merge_buckets, "d_info over a
+ * view") the caller has to keep that.
  * With valid == 0 every probe that takes part gets pos = end = 0 and END.
  * With m == 0 nothing is launched or stored.
  * The write set is exactly d_out[0, m). No workspace and no context scratch:
@@ -840,7 +844,10 @@ uint64_t honu_sizeof_list_row(void);
  * d_range_off[0, m + 1), d_total[0], d_rows[0, w) and d_keys_out[0, 29 w).
  * Optionals. d_order, d_info and d_keys_out may be NULL; d_info needs
  * d_order. Without d_order, record is HONU_SEEK_NONE. An index of d_order
- * that is not below n reads d_info row n - 1, as in honu_key_seek. d_rows may
+ * that is not below n reads d_info row n - 1, as in honu_key_seek: d_info is
+ * indexed by record and clamped by the column's rows, so TOMBSTONE answers for
+ * the column only while every index in its valid rows is below n (over a view
+ * of a bucketed column see honu_key_merge_buckets, "d_info over a view"). d_rows may
  * be NULL only with cap == 0: a counting call. With m == 0, d_range_off[0] =
  * 0 and d_total[0] = 0; with v == 0 every count is 0.
  * Asynchronous on `stream`, no host synchronisation, no allocation, no
@@ -971,7 +978,11 @@ uint64_t honu_key_filter_workspace(uint64_t cap);
  * over d_obj_off[1..objects], every offset clamped to v, as the list's LATEST
  * mode reads them (a pos at or past the last offset reads the last object). r
  * = d_latest[j]; an r that is not below n reads info row n - 1, the convention
- * of honu_key_seek and honu_key_list. The row goes when d_info[r].tombstone !=
+ * of honu_key_seek and honu_key_list, and with the same condition: d_info is
+ * indexed by record and clamped by the column's rows, so HONU_FILTER_DELETED
+ * answers for the column only while every index in its valid rows is below n
+ * (over a view of a bucketed column see honu_key_merge_buckets, "d_info over a
+ * view"). The row goes when d_info[r].tombstone !=
  * 0. So every version row of a deleted object goes, its live older versions
  * included; a tombstone version of an object whose latest version is live
  * stays (Versions() "includes tombstone versions", collection.go:106-107);
@@ -1098,7 +1109,10 @@ uint64_t honu_key_next_workspace(uint64_t m);
  * wrap; FOUND = pos < end; the stored latest scalar (P, V) = BE32 of bytes
  * [25, 29) and BE64 of bytes [17, 25) of row end - 1; LIVE = FOUND without
  * d_info (Has), FOUND && !d_info[d_order[end - 1]].tombstone with d_order and
- * d_info (an index not below n reads info row n - 1, as honu_key_seek); and
+ * d_info (an index not below n reads info row n - 1, as honu_key_seek: d_info
+ * is indexed by record and clamped by the column's rows, so LIVE answers for
+ * the column only while every index in its valid rows is below n; over a view
+ * of a bucketed column see honu_key_merge_buckets, "d_info over a view"); and
  * its rank r, the number of earlier requests of this call, in request order,
  * that count and have the same 17 bytes. FOUND and LIVE report the column as
  * it is stored, whatever earlier requests do to the object.
@@ -1473,7 +1487,27 @@ int32_t honu_key_route(honu_ctx *ctx, const uint8_t *d_ids, uint64_t id_stride,
  * of a bucket is valid. A view (d_sorted + 29 off[c], d_order + off[c],
  * d_count + c, rows) is an input of every per-bucket call above, and a
  * honu_key_delete over a view that writes its d_valid_out into a count array
- * produces the next call's d_count_a. honu_key_route's outputs are a bucketed
+ * produces the next call's d_count_a.
+ * d_info over a view. honu_key_seek, honu_key_list, honu_key_filter and
+ * honu_key_next index d_info by record and clamp the index by n, the rows of
+ * the column they are given; over a view that is the view's rows. A per-bucket
+ * call given d_info therefore answers for a view only while every index in the
+ * view's valid rows is below the view's rows; an index at or above them reads
+ * info row rows - 1, and nothing signals it. Per-bucket numbering (d_order_b =
+ * d_local, d_base the buckets' record counts) keeps the condition while a
+ * bucket holds no more records than rows. This call is tight: after a
+ * honu_key_delete over a view the next merge squeezes the removed rows out,
+ * the bucket then has fewer rows than records, and every later record of it
+ * has an index at or above the view's rows. So a delete over a view must be
+ * followed by a honu_key_reclaim of that bucket (its view, its d_count entry
+ * and its record arrays) before the merge that squeezes it; d_base[c] is then
+ * that call's d_kept. The one-numbering form (d_order_b and d_base NULL, a
+ * scalar b_base) numbers a bucket's records above its rows from the first
+ * batch on and cannot be used with d_info over views. honu_key_objects,
+ * honu_key_fetch, honu_key_compare and honu_key_delete take no d_info, and
+ * honu_key_reclaim only moves its rows, by record and bounded by nrec: none of
+ * them has such a condition.
+ * honu_key_route's outputs are a bucketed
  * column as they stand: d_keys_out the rows, d_bucket_off the offsets (its
  * first k + 1 entries are used; the two tail classes lie behind
  * d_bucket_off[k] and reach no bucket), d_local the order.
